@@ -9,15 +9,19 @@ its 2-bit plane -- through isx_pipe_submit_planes: the pipe's host threads copy 
 make the 32-byte reference-delta wire records by XOR against them, hipMemcpyAsync brings them in, the batch is profiled ONCE
 on the device (k_pileup_dense: difference-array pileup in LDS, SNV call epilogue, linkage chain) and its tables are copied
 back to pinned host memory (isx_pipe_collect); staging / copy-in / pass / copy-out of consecutive batches overlap in the
-pipe.  (Round 4's headline replayed pre-staged pinned images: that is the extra `c5_staged_replay_gbp_per_s` now.)  Before the timed steps ONE untimed pass checks every batch's
-tables on the host (C5Run.verify_pass); every timed batch's row counts must equal that pass's.  N > 1: the 8 LPT shards
-of the database are dealt over the ranks (strong scaling; no data-path collective; one final RCCL gather of the SNV
-tables after the timed region, reported separately).  `python bench.py --gpus N` without a launcher starts its N ranks
+pipe.  (Round 4's headline replayed pre-staged pinned images: that is the extra `c5_staged_replay_gbp_per_s` now.)  N > 1: the 8 LPT shards
+of the database are dealt over the ranks (strong scaling; no data-path collective).  `python bench.py --gpus N` without a launcher starts its N ranks
 itself (torch.distributed.run on 127.0.0.1).
 
-Prints ONE short JSON line on rank 0 (contract in the task statement: metric / value / ... / config / roofline /
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: it sets up, warms up, times the N steps and
+prints the line.  `--dump-outputs DIR` also writes what the last timed pass handed back (OutputDump).  Everything else is `--full`:
+before the timed steps ONE untimed pass checks every batch's tables on the host (C5Run.verify_pass) and every timed batch's row counts
+and row checksum must equal that pass's; N > 1: one final gather of the tables after the timed region, reported separately; and the
+extra legs below.
+
+Prints ONE short JSON line on rank 0 (contract in the task statement: metric / value / ... / config / roofline; with --full also
 cpu_baseline + cpu_baseline_python on the same configuration) and writes the full record -- every leg's detail -- to
-bench_detail.json (--detail): `c5` (the headline in full), `c2_stream` (configs[1] streamed, the round-3 headline),
+bench_detail.json (--detail): `c5` (the headline in full), and with --full `c2_stream` (configs[1] streamed, the round-3 headline),
 `roofline_c2_resident` / `roofline_lds` / `roofline_observation_kernel` (the kernels alone over resident C2 batches),
 `mm_on`, `linkage` (C3), `bam_sharded` (one BAM over the ranks), `profile_bam` / `c5_bam` (BAM on disk -> SplitObjects),
 `cpu_baseline_c2` / `cpu_baseline_python_c2`.
@@ -653,12 +657,13 @@ class C5Run:
             self.stage_all()
         stream(self.pipe, self.ws, len(self.ws), self.depth, check=check, wires=self.wires if staged else None)
 
-    def run(self, passes, stats=None, keep_last=False, staged=False):
+    def run(self, passes, stats=None, keep_last=False, staged=False, last_pass=None):
         """passes over the rank's batches.  staged False (the headline): every batch handed over from the caller's arrays --
         isx_pipe_submit_planes: reference planes copied into pinned staging, records made by the XOR pass, DMA, kernels, tables back, all
-        inside the step.  staged True: the pinned images of stage_all() replayed (DMA + kernels + tables back)."""
+        inside the step.  staged True: the pinned images of stage_all() replayed (DMA + kernels + tables back).  last_pass: see stream()."""
         n = len(self.ws)
-        return stream(self.pipe, self.ws, n * passes, self.depth, stats, keep_last=keep_last, wires=self.wires if staged else None)
+        return stream(self.pipe, self.ws, n * passes, self.depth, stats, keep_last=keep_last, wires=self.wires if staged else None,
+                      last_pass=last_pass)
 
     def gather_pass(self):
         """one untimed pass whose tables are KEPT: what this rank contributes to the path's one collective (the final gather of the
@@ -791,9 +796,11 @@ class C5Run:
                             "traffic_source": _pmc_source("c5_dense_linkage_bytes_per_launch"),
                             # the same kernel time priced on SURVEY 8(d)'s byte model of the naive formulation (12 B per kept observation
                             # with linkage + 1 B per position of reference + 28 B per covered position out) instead of this build's format
-                            # bytes -- for comparison only: `frac` above is the stricter figure
+                            # bytes -- for comparison only: `frac` above is the stricter figure.  The covered positions come from verify_pass
+                            # (bench.py --full); a plain run leaves it out
                             "survey_8d_model": {"bytes_per_pass": n_obs * 12 + n_pos + int(getattr(self, "covered", 0) or n_pos) * 28,
-                                                "frac": ((n_obs * 12 + n_pos + int(getattr(self, "covered", 0) or n_pos) * 28) / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_ms else 0.0},
+                                                "frac": ((n_obs * 12 + n_pos + int(getattr(self, "covered", 0) or n_pos) * 28) / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_ms else 0.0}
+                                               if getattr(self, "covered", None) is not None else None,
                             "bound_of_the_pass": "host stager %.1f ms + pcie copy-in %.1f ms, overlapped, of %.1f ms" % (tot("encode_ms"), tot("h2d_ms"), dt_max / passes * 1e3)},
                "roofline_pcie": {"bound": "pcie", "direction": "host->device", "achieved": tot("h2d_bytes") / (dt_max / passes) / 1e9, "peak": PCIE_PEAK_GBS,
                                  "unit": "GB/s", "frac": tot("h2d_bytes") / (dt_max / passes) / 1e9 / PCIE_PEAK_GBS, "bytes_per_pass": tot("h2d_bytes"),
@@ -811,6 +818,120 @@ class C5Run:
         cb = cpu_baseline(wo, budget_s=14.0, min_s=8.0)
         cp = cpu_baseline_python(wo, n_splits=200, budget_s=22.0, min_s=12.0)
         return cb, cp
+
+
+class OutputDump:
+    """--dump-outputs: what the last timed pass handed back to the caller, as .npy files that two builds can be compared by.  Every batch
+    of that pass contributes, taken while its slot is held (stream(last_pass=...)): its row counts and the library's checksum over the
+    bytes of ALL its SNV + LD rows, its SNV rows and LD rows (copied whole; a seeded sample of them is written), and coverage +
+    clonality over a few seeded blocks of BLOCK positions (slices of the shrunk hand-back forms, nothing densified).  Positions are flat
+    over the pass (the batch's offset + its own position).  Every value written is finite: clonality and the LD statistics keep only
+    their defined values, with <name>_row naming the rows they belong to.  The samples depend on the seed, the batch and its row count only, so equal
+    builds write equal files; the caps keep the whole under ~45 MB (float64 for positions and LD statistics, float32 for counts and
+    codes).  Inside the timed pass a batch costs two row copies and a few slices (capture_ms in the line)."""
+
+    SEED = 20250101
+    BLOCK = 4096
+    SNV_ROWS, LD_ROWS, COV_POSITIONS = 1 << 19, 1 << 17, 1 << 18         # totals over the pass, split evenly over its batches
+    UNDEFINED_OK = ("clonality", "ld_r2", "ld_d_prime", "ld_r2_normalized", "ld_d_prime_normalized")
+
+    def __init__(self, ws, min_cov):
+        n = len(ws)
+        self.min_cov = int(min_cov)
+        self.offset = np.r_[0, np.cumsum([int(w["n_pos"]) for w in ws])][:-1].astype(np.int64)
+        self.k_snv, self.k_ld = max(1, self.SNV_ROWS // n), max(1, self.LD_ROWS // n)
+        self.blocks = []
+        for i, w in enumerate(ws):
+            n_pos, L = int(w["n_pos"]), self.BLOCK
+            nb = (n_pos + L - 1) // L
+            b = np.sort(np.random.default_rng([self.SEED, i, 0]).choice(nb, min(nb, max(1, self.COV_POSITIONS // n // L)), replace=False))
+            self.blocks.append([(int(k) * L, min(int(k) * L + L, n_pos)) for k in b])
+        self.got = [None] * n
+        self.capture_s = 0.0
+
+    def positions(self, i):
+        return np.concatenate([np.arange(lo, hi, dtype=np.int64) for lo, hi in self.blocks[i]])
+
+    def _rows(self, i, tag, n, k):
+        if n <= k:
+            return np.arange(n)
+        return np.sort(np.random.default_rng([self.SEED, i, tag, n]).choice(n, k, replace=False))
+
+    def _block(self, r, lo, hi):
+        """coverage (exact where the hand-back lists a saturated position) and clonality of positions lo .. hi - 1 of one batch"""
+        if "cov16" in r:
+            cov = r["cov16"][lo:hi].astype(np.int64)
+        elif "cov8" in r:
+            cov = r["cov8"][lo:hi].astype(np.int64)
+        else:                                       # lean slot: 4-bit plane + 16-bit rows of the windows beyond 15 (engine.dense_cov)
+            nib = r["cov4"][lo >> 1:(hi + 1) >> 1]  # (lo is even: blocks start at multiples of BLOCK)
+            cov = np.empty(2 * len(nib), np.int64)
+            cov[0::2], cov[1::2] = nib & 15, nib >> 4
+            cov = cov[:hi - lo]
+            W, rw = int(r["cov_window"]), r["cov_row_win"]
+            for k in np.flatnonzero((rw >= lo // W) & (rw <= (hi - 1) // W)):
+                w0 = int(rw[k]) * W
+                s, e = max(lo, w0), min(hi, w0 + W)
+                cov[s - lo:e - lo] = r["cov_rows"][k, s - w0:e - w0]
+        if "saturated" in r:                        # (unordered)
+            g = r["saturated"]["gpos"].astype(np.int64)
+            m = (g >= lo) & (g < hi)
+            cov[g[m] - lo] = r["saturated"]["coverage"][m]
+        if "clon" in r:
+            clon = r["clon"][lo:hi].astype(np.float32)
+        else:                                       # 1.0 at min_cov and beyond, NaN below, the listed values (engine.dense_clon)
+            clon = np.where(cov >= self.min_cov, np.float32(1.0), np.float32(np.nan)).astype(np.float32)
+            cs = r["clon_sparse"]
+            a, b = np.searchsorted(cs["gpos"], [lo, hi])        # (ascending gpos)
+            clon[cs["gpos"][a:b].astype(np.int64) - lo] = cs["clon"][a:b]
+        return cov, clon
+
+    def _coverage(self, r, i):
+        got = [self._block(r, lo, hi) for lo, hi in self.blocks[i]]
+        return np.concatenate([c for c, _ in got]), np.concatenate([c for _, c in got])
+
+    def __call__(self, i, r):
+        t0 = time.perf_counter()
+        cov, clon = self._coverage(r, i)
+        self.got[i] = {"sizes": (int(r["sizes"]["n_snv"]), int(r["sizes"]["n_ld"]), int(r["sizes"]["n_edges"])),
+                       "checksum": int(r["rows_checksum"]), "snv": r["snv"].copy(), "ld": r["ld"].copy(), "cov": cov, "clon": clon}
+        self.capture_s += time.perf_counter() - t0
+
+    def write(self, out_dir):
+        if any(g is None for g in self.got):
+            raise RuntimeError("bench.py --dump-outputs: the last timed pass did not hand every batch back")
+        os.makedirs(out_dir, exist_ok=True)
+        got, off = self.got, self.offset
+        for i, g in enumerate(got):
+            g["snv"] = g["snv"][self._rows(i, 1, len(g["snv"]), self.k_snv)]
+            g["ld"] = g["ld"][self._rows(i, 2, len(g["ld"]), self.k_ld)]
+        cat = lambda f: np.concatenate([f(i, g) for i, g in enumerate(got)])
+        out = {"batch_rows": np.array([g["sizes"] for g in got], np.float64),
+               "batch_rows_checksum": np.array([(g["checksum"] >> 32, g["checksum"] & 0xFFFFFFFF) for g in got], np.float64),
+               "coverage_position": cat(lambda i, g: self.positions(i) + off[i]).astype(np.float64),
+               "coverage": cat(lambda i, g: g["cov"]).astype(np.float32),
+               "clonality": cat(lambda i, g: g["clon"]).astype(np.float32),
+               "snv_position": cat(lambda i, g: g["snv"]["gpos"].astype(np.int64) + off[i]).astype(np.float64),
+               "snv_counts": cat(lambda i, g: g["snv"]["cnt"]).astype(np.float32),
+               "ld_position_a": cat(lambda i, g: g["ld"]["gpos_a"].astype(np.int64) + off[i]).astype(np.float64),
+               "ld_position_b": cat(lambda i, g: g["ld"]["gpos_b"].astype(np.int64) + off[i]).astype(np.float64)}
+        for f in ("mm", "con_base", "var_base", "allele_count", "cls", "cryptic", "ref_base"):
+            out["snv_" + f] = cat(lambda i, g: g["snv"][f]).astype(np.float32)
+        for f in ("mm", "allele_A", "allele_a", "allele_B", "allele_b", "total", "countAB", "countAb", "countaB", "countab"):
+            out["ld_" + f] = cat(lambda i, g: g["ld"][f]).astype(np.float32)
+        for f in ("r2", "d_prime", "r2_normalized", "d_prime_normalized"):
+            out["ld_" + f] = cat(lambda i, g: g["ld"][f]).astype(np.float64)
+        # clonality is NaN below min_cov and an LD statistic NaN where it is undefined: these columns keep their defined values only,
+        # and <name>_row says which rows of their table (coverage_position / the ld_ columns) those are -- every file is finite
+        for k in self.UNDEFINED_OK:
+            ok = np.isfinite(out[k])
+            out[k], out[k + "_row"] = out[k][ok], np.flatnonzero(ok).astype(np.float64)
+        for k, v in out.items():
+            if not np.isfinite(v).all():
+                raise AssertionError("bench.py --dump-outputs: %s holds values that are not finite" % k)
+        for k, v in out.items():
+            np.save(os.path.join(out_dir, k + ".npy"), v)
+        return {"dir": out_dir, "files": len(out), "bytes": int(sum(v.nbytes for v in out.values())), "capture_ms": round(self.capture_s * 1e3, 2)}
 
 
 def rank_threads_sweep(local, lut, fb, depth, scale=1.0, threads=(2, 4, 8, 16), passes=6):
@@ -1006,9 +1127,10 @@ def make_variants(w, n):
         return list(ex.map(lambda k: synth.shifted_variant_segs(w, k), range(n)))
 
 
-def stream(pipe, variants, n_steps, depth, stats=None, keep_last=False, check=None, wires=None, keyed=False):
+def stream(pipe, variants, n_steps, depth, stats=None, keep_last=False, check=None, wires=None, keyed=False, last_pass=None):
     """n_steps batches through the pipe, at most `depth` in flight; returns the last collected result.  check(i, result) is
-    called on every collected batch (untimed verification passes only).  wires: the batches staged ahead of time
+    called on every collected batch (untimed verification passes only); last_pass(i, result) on the batches of the final pass
+    over `variants` only (OutputDump: a small sample, taken while the slot is held).  wires: the batches staged ahead of time
     (Pipe.stage_reads) -- a submit is then DMA + kernels only (isx_pipe_submit_wire)."""
     tickets, done, last = [], 0, None
     link = pipe.enable_linkage
@@ -1020,6 +1142,8 @@ def stream(pipe, variants, n_steps, depth, stats=None, keep_last=False, check=No
             stats.append((r["stats"], dict(r["sizes"], rows_checksum=r["rows_checksum"])))
         if check is not None:
             check(done % len(variants), r)
+        if last_pass is not None and done >= n_steps - len(variants):
+            last_pass(done % len(variants), r)
         if keep_last and done == n_steps - 1:
             last = {"snv": r["snv"].copy()}
         pipe.release(tickets[done])
@@ -1254,9 +1378,18 @@ def main():
     ap.add_argument("--only-c5", action="store_true", help="the headline alone: no C2 legs, no BAM legs, no CPU baselines (debug)")
     ap.add_argument("--detail", default=os.path.join(REPO, "bench_detail.json"), help="where the full record goes (the printed line is a digest)")
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the untimed verify pass and the check of every timed batch against it, the staged and "
+                         "resident-reference replays, the CPU baselines, the C2 / mm / linkage / BAM legs, the threads sweep, the final gather "
+                         "(N > 1); the --no-* / --only-* options choose among them.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed pass handed back (row counts + checksums of every batch, seeded samples "
+                         "of the SNV / LD rows, coverage + clonality at seeded positions) as DIR/<name>.npy; N > 1: rank 0's share")
     args = ap.parse_args()
-    if args.only_c5:
+    if args.only_c5 or not args.full:
         args.no_c2_leg = args.no_resident_leg = args.no_mm_leg = args.no_linkage_leg = args.no_cpu_baseline = args.no_bam_leg = True
+    if not args.full:
+        args.no_rank_sweep = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -1287,9 +1420,11 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local) if (world == 1 or use_nccl) else torch.device("cpu")
     numa_node = None if args.no_bind else bind_to_gpu_numa_node(torch, local)
-    ctx = engine.Context(local)
     lut, fb = util.load_lut()
-    ctx.set_null_model(lut, fb)
+    ctx = None
+    if args.full:                               # (the extra legs' context: the headline runs in its own, ctx5 below)
+        ctx = engine.Context(local)
+        ctx.set_null_model(lut, fb)
     host_threads = args.host_threads or max(2, min(48, host_cpus() // world))
 
     def barrier():
@@ -1307,8 +1442,9 @@ def main():
     ctx5.set_null_model(lut, fb)
     c5 = C5Run(ctx5, rank, world, host_threads, depth=args.depth, scale=args.scale, stage_async=args.queued_submit)
     c5_ref_registered = bool(c5.ref_registered)
-    _trace("C5 verify pass")
-    c5.verify_pass()                            # untimed: every batch's tables checked on the host; also warms every slot
+    if args.full:
+        _trace("C5 verify pass")
+        c5.verify_pass()                        # untimed: every batch's tables checked on the host; also warms every slot
     # N > 1: the job is the same whole database (strong scaling), so a rank's pass shrinks to a few ms -- a STEP is then PPS passes
     # back to back (the rate is what is reported; the timed region must be long against a barrier's jitter)
     PPS = 1 if world == 1 else int(os.environ.get("ISX_BENCH_PASSES_PER_STEP", 2 * world))
@@ -1317,9 +1453,10 @@ def main():
     barrier()
     torch.cuda.synchronize()
     stats = []
+    dump = OutputDump(c5.ws, c5.pipe.min_cov) if (args.dump_outputs and rank == 0) else None
     cpu0, thr0 = time.process_time(), cgroup_throttled_ms()
     t0 = time.perf_counter()
-    c5.run(args.steps * PPS, stats)
+    c5.run(args.steps * PPS, stats, last_pass=dump)
     torch.cuda.synchronize()
     dt_mine = time.perf_counter() - t0
     # what the timed passes cost the HOST: cpu time of all threads of this process per wall second (stager threads, finishers, the DMA's
@@ -1328,7 +1465,9 @@ def main():
                 "throttled_ms_per_pass": None if thr0 is None else (cgroup_throttled_ms() - thr0) / (args.steps * PPS)}
     barrier()
     dt = time.perf_counter() - t0
-    c5.check_timed(stats)
+    if args.full:
+        c5.check_timed(stats)
+    dumped = dump.write(args.dump_outputs) if dump is not None else None
     bases_all = c5.bases
     per_rank = None
     if world > 1:
@@ -1350,7 +1489,7 @@ def main():
     # the one collective of the path: the final gather of ONE pass's whole profile to rank 0 -- every batch's SNV rows and LD rows and
     # the per-scaffold summaries -- outside the timed steps, timed on its own
     gather_ms = gathered = None
-    if world > 1:
+    if world > 1 and args.full:
         mine_tables = c5.gather_pass()
         torch.cuda.synchronize()
         barrier()
@@ -1367,7 +1506,7 @@ def main():
     if per_rank is not None:
         head["per_rank"] = per_rank
         head["final_gather"] = gathered
-    if (world == 1 and rank == 0 and (not args.only_c5 or os.environ.get("ISX_BENCH_STAGED"))) or world > 1:
+    if args.full and ((world == 1 and rank == 0 and (not args.only_c5 or os.environ.get("ISX_BENCH_STAGED"))) or world > 1):
         # (N > 1: every rank replays its own staged images -- the device side of the scaling curve, free of the host stager's share of
         # the node's cpus; aggregated below)
         rep = c5.staged_replay(passes=4 * PPS)
@@ -1377,7 +1516,7 @@ def main():
             dist.all_reduce(u, op=dist.ReduceOp.MAX)
             rep = dict(rep, ms_per_pass=float(u.item()), gbp_per_s=bases_all / (float(u.item()) * 1e-3) / 1e9, note="max over ranks of a rank's own replay time")
         head["staged_replay"] = rep
-    if rank == 0 and world == 1 and (not args.only_c5 or os.environ.get("ISX_BENCH_RESIDENT_REF")):
+    if args.full and rank == 0 and world == 1 and (not args.only_c5 or os.environ.get("ISX_BENCH_RESIDENT_REF")):
         head["resident_reference"] = c5.resident_reference_passes()         # (last: the wires keep their device copies from here on)
     cb = cp = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -1411,7 +1550,8 @@ def main():
                        "reference_registered": c5_ref_registered,
                        "pipe_depth": args.depth, "pileup_cus": 256 - 8 * C5_RESERVE_CUS, "lean_slots": LEAN_SLOTS, "host_threads_per_rank": host_threads, "cgroup_cpus": cgroup_cpus(),
                        "numa_node": numa_node, "parallelism": "genome-sharded x%d%s" % (world, " (ranks share %d GPU)" % n_dev if shared else ""),
-                       "verified": "per-batch checks in an untimed pass (largest batch: exact coverage + per-base SNV counts from the host); timed batches: row counts + checksum of the SNV / LD bytes equal"},
+                       "verified": ("per-batch checks in an untimed pass (largest batch: exact coverage + per-base SNV counts from the host); timed batches: row counts + checksum of the SNV / LD bytes equal"
+                                    if args.full else "not in this run (bench.py --full checks every batch)")},
             "roofline": {k: head["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
                                                             "algorithmic_bytes_per_launch", "kernel_ms_avg", "launches", "positions_per_s", "survey_8d_model", "bound_of_the_pass")},
             "h2d_bytes_per_base": head["roofline_pcie"]["bytes_per_profiled_base"], "pcie_frac": head["roofline_pcie"]["frac"],
@@ -1431,6 +1571,8 @@ def main():
             out["final_gather"] = gathered
         if per_rank is not None:
             out["per_rank"] = per_rank
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if cb is not None:
             detail["cpu_baseline"], detail["cpu_baseline_python"] = cb, cp
             out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -1522,7 +1664,8 @@ def main():
         if os.environ.get("ISX_BENCH_DETAIL_STDERR"):
             print(json.dumps(detail), file=sys.stderr, flush=True)
         print(json.dumps(out), flush=True)
-    ctx.close()
+    if ctx is not None:
+        ctx.close()
     if world > 1:
         barrier()
         dist.destroy_process_group()

@@ -446,7 +446,7 @@ def test_bench_two_ranks_control_flow(tmp_path):
     env = dict(os.environ, ISX_DIST_BACKEND="gloo", ISX_DEVICE="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
     r = util.run_group([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29577", os.path.join(repo, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--detail", str(tmp_path / "d.json")],
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--full", "--detail", str(tmp_path / "d.json")],
                        env=env, timeout=420)
     j = _bench_line(r)
     assert j["n_gpus"] == 2 and j["world_size_seen"] == 2 and j["backend"] == "gloo"
@@ -468,7 +468,7 @@ def test_bench_eight_ranks_control_flow(tmp_path):
     repo = os.path.dirname(util.GOLD.rstrip("/")).rsplit("/tests", 1)[0]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ISX_DIST_BACKEND", "ISX_DEVICE")}
     r = util.run_group([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--scale", "0.04", "--depth", "2",
-                        "--host-threads", "2", "--only-c5", "--detail", str(tmp_path / "d.json")], env=env, timeout=600)
+                        "--host-threads", "2", "--only-c5", "--full", "--detail", str(tmp_path / "d.json")], env=env, timeout=600)
     j = _bench_line(r)
     assert j["n_gpus"] == 8 and j["world_size_seen"] == 8 and j["value"] > 0 and j["passes_per_step"] == 16
     assert len(j["per_rank"]["pass_ms"]) == 8 and min(j["per_rank"]["batches"]) >= 1
@@ -494,6 +494,31 @@ def test_bench_starts_its_own_ranks(tmp_path):
     r2 = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--scale", "0.05", "--only-c5"],
                         env=env2, capture_output=True, text=True, timeout=300)
     assert r2.returncode != 0 and "WORLD_SIZE=1" in (r2.stderr + r2.stdout)
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps passes of the headline and no extra leg; --dump-outputs writes what the last timed
+    pass handed back, finite float32 / float64 only and within 64 MB, the same files whatever the number of steps (the inputs are fixed)"""
+    import sys
+    repo = os.path.dirname(util.GOLD.rstrip("/")).rsplit("/tests", 1)[0]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ISX_DIST_BACKEND", "ISX_DEVICE")}
+    dumps = []
+    for steps in (1, 3):
+        out = tmp_path / ("dump%d" % steps)
+        r = util.run_group([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--scale", "0.05",
+                            "--dump-outputs", str(out), "--detail", str(tmp_path / "d.json")], env=env, timeout=420)
+        j = _bench_line(r)
+        assert j["metric"] == "Gbp profiled/s" and j["value"] > 0 and j["steps"] == steps and j["ms_per_step"] > 0
+        assert j["roofline"]["launches"] == steps * j["config"]["batches_per_step"]
+        assert "cpu_baseline" not in j and "c5_staged_replay_gbp_per_s" not in j and "c2_stream_gbp_per_s" not in j
+        dumps.append({f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert len(a["batch_rows"]) == j["config"]["batches_per_step"] and a["batch_rows"][:, 0].sum() > 0 and len(a["snv_position"]) > 0
+    assert len(a["coverage"]) == len(a["coverage_position"]) > 0 and (a["coverage"] > 0).any()
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all(), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
 @pytest.mark.parametrize("name", ["synth_m1", "synth_skipmm", "synth_m1_ld", "synth_skipmm_ld", "c3_split"])

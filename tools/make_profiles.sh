@@ -7,12 +7,12 @@ TAG=${1:-r06}
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 B="python $REPO/bench.py"
 T="python $REPO/tools/pmc_target.py"
 # kernel time: the headline leg, and the resident launches the counters are collected on
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c5 -o $TAG -- $B --only-c5 --steps 3 --warmup 1 --detail /tmp/d.json > $OUT/trace_c5.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c5 -o $TAG -- $B --full --only-c5 --steps 3 --warmup 1 --detail /tmp/d.json > $OUT/trace_c5.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c2 -o $TAG -- $T > $OUT/trace_c2.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c5b -o $TAG -- $T --c5 > $OUT/trace_c5b.log 2>&1
 # hardware counters: their own passes, no tracing

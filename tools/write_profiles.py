@@ -77,7 +77,7 @@ reference-delta kernel).
 c5 = detail["c5"]
 open('profiles/%s_c5_kernel_stats.md' % tag, 'w').write(f'''# Round {rnd} -- rocprofv3 --kernel-trace --stats, bench.py headline (configs[4]: the whole 1000-genome database through one GPU)
 
-Command (tools/make_profiles.sh): `rocprofv3 --kernel-trace --stats --output-format csv -d ... -- python bench.py --only-c5 --steps 3 --warmup 1`
+Command (tools/make_profiles.sh): `rocprofv3 --kernel-trace --stats --output-format csv -d ... -- python bench.py --full --only-c5 --steps 3 --warmup 1`
 (verification pass + 1 warm-up + 3 timed passes of {c5["batches"]} batches each; the k_pileup_dense<true, 32, true> rows are those batches).
 Un-profiled bench line of the same box: **{line["value"]:.1f} Gbp/s** ({line["ms_per_step"]:.1f} ms per pass; per pass: {c5["stages_ms_per_pass"]});
 pileup kernel {c5["roofline"]["kernel_ms_per_pass"]:.1f} ms per pass on {c5["roofline"]["bytes_per_position"]:.2f} algorithmic bytes per position;
