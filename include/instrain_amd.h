@@ -327,6 +327,65 @@ int isx_compare_scaffolds(isx_batch *a, isx_batch *b, int32_t n_scaffolds, const
                           double min_freq, isx_compare_level *out, int64_t *n_snp_rows, float *device_ms);
 int isx_compare_fetch_snps(isx_batch *a, isx_compare_snp *out);
 
+/* ---- gene profiling (GeneProfile.py:304-707 profile_genes_from_profile: `inStrain profile -g genes.fna`) ----
+ * A gene set lives on the device for as long as the caller keeps it: coordinates + the genes' own letters (upper-case
+ * A/C/G/T/N as in the .fna, gene orientation), uploaded once.  Genes of one scaffold are consecutive in the set.
+ * A call names the scaffolds of its flat space (scaffold_bounds, as for isx_batch_summarize) and, per scaffold s, the genes
+ * [gene_first[s], gene_last[s]) of the set that lie on it; the call's genes are those ranges in scaffold order ("call order"). */
+typedef struct isx_genes isx_genes;
+
+typedef struct {
+    int64_t start, end;         /* 0-based inclusive scaffold coordinates (prodigal's start - 1, end - 1); end - start + 1 letters */
+    int64_t seq_off;            /* offset of the gene's letters in the sequence buffer handed to isx_genes_create */
+    int32_t strand;             /* +1, or -1: the letters are the reverse complement of the scaffold slice */
+    int32_t pad;
+} isx_gene;
+
+/* coverage half, one row per (call gene, mm level): calc_gene_coverage / calc_gene_clonality (:352-422) over the gene's positions
+ * inside its scaffold (the interval is clipped to it, gene_length stays end - start + 1).  Exact sums; clonality summed in fp64 in a
+ * fixed order (two runs give identical bytes). */
+typedef struct {
+    uint64_t sum_cov;           /* sum of the coverage cumulated over levels <= mm */
+    uint32_t nonzero;           /* positions with cumulative coverage > 0 (breadth * gene_length) */
+    uint32_t counted;           /* positions with a clonality at a level <= mm (breadth_minCov * gene_length) */
+    double sum_clon;            /* nucl_diversity = 1 - sum_clon / counted */
+} isx_gene_cov;
+
+/* isx_batch_profile_genes: scaffold_flags[n_scaffolds][n_mm_bins] bits */
+#define ISX_GENE_LEVEL_PRESENT 1    /* the level is a key of the scaffold's covT / clonT */
+#define ISX_GENE_COV_ANY 2          /* the scaffold's coverage cumulated over levels <= mm is not empty */
+#define ISX_GENE_CLON_ANY 4         /* some position of the scaffold has a clonality at a level <= mm */
+
+/* SNV half (calc_gene_snp_counts :448-598), one row per (call gene, mm level): the SNV rows current at that level -- per position the
+ * row of its highest mm <= level -- inside the gene; N / S = the mutation type of the position's highest-mm row */
+typedef struct {
+    uint32_t divergent, sns, sns_n, sns_s, snv, snv_n, snv_s;
+} isx_gene_snv_count;
+
+/* characterize_SNPs (:600-707): one record per SNV row; type 0 = not classified (not its position's highest-mm row, or an
+ * allele_count outside {1, 2}) */
+typedef struct {
+    int32_t gene;               /* gene-set index: the covering gene (N, S), the first covering gene in position order (M), -1 (I) */
+    int32_t k;                  /* position - gene start (N, S) */
+    uint8_t type;               /* 0, 'I', 'M', 'N', 'S' */
+    uint8_t aa_old, aa_new;     /* N: the amino acids (ASCII) of the changed codon */
+    uint8_t n_genes;            /* covering genes, saturating at 255 */
+    uint32_t pad;
+} isx_gene_mutation;
+
+int isx_genes_create(isx_ctx *ctx, int64_t n_genes, const isx_gene *genes, const char *seq, int64_t seq_bytes, isx_genes **out);
+void isx_genes_destroy(isx_genes *g);
+/* count_sites (:428-486) of every gene of the set: sites[n_genes][2] = (S_sites, N_sites), codons in order, fp64 */
+int isx_genes_sites(isx_genes *g, double *sites, float *device_ms);
+/* coverage half on a run batch (or a collected non-lean pipe slot): cov_out[n_call_genes][n_mm_bins] */
+int isx_batch_profile_genes(isx_batch *b, isx_genes *g, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *gene_first,
+                            const int32_t *gene_last, isx_gene_cov *cov_out, uint8_t *scaffold_flags, float *device_ms);
+/* SNV half on host rows in (gpos, mm) order over the same kind of flat space (a batch's fetched rows, or a stored table laid out by the
+ * caller): mut_out[n_snv], cnt_out[n_call_genes][n_levels]; every row's mm < n_levels */
+int isx_genes_profile_snvs(isx_genes *g, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *gene_first,
+                           const int32_t *gene_last, int64_t n_snv, const isx_snv *snv, int32_t n_levels, isx_gene_mutation *mut_out,
+                           isx_gene_snv_count *cnt_out, float *device_ms);
+
 /* ---- streaming hand-over: profile a stream of batches, each exactly once ----
  * What production does (the reference's analogue is the command / result queue pair around its worker pool,
  * profile_controller.py:157-193, 243-271): batches arrive from the host, are profiled once and their tables go

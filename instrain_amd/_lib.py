@@ -142,6 +142,15 @@ COMPARE_SNP_DT = np.dtype([("gpos", "<u4"), ("mm", "<u2"), ("consensus_snp", "u1
 assert COMPARE_SNP_DT.itemsize == 48
 
 
+GENE_DT = np.dtype([("start", "<i8"), ("end", "<i8"), ("seq_off", "<i8"), ("strand", "<i4"), ("pad", "<i4")])
+GENE_COV_DT = np.dtype([("sum_cov", "<u8"), ("nonzero", "<u4"), ("counted", "<u4"), ("sum_clon", "<f8")])
+GENE_SNV_COUNT_DT = np.dtype([(n, "<u4") for n in ("divergent", "sns", "sns_n", "sns_s", "snv", "snv_n", "snv_s")])
+GENE_MUTATION_DT = np.dtype([("gene", "<i4"), ("k", "<i4"), ("type", "u1"), ("aa_old", "u1"), ("aa_new", "u1"), ("n_genes", "u1"),
+                             ("pad", "<u4")])
+assert GENE_DT.itemsize == 32 and GENE_COV_DT.itemsize == 24 and GENE_SNV_COUNT_DT.itemsize == 28 and GENE_MUTATION_DT.itemsize == 16
+GENE_LEVEL_PRESENT, GENE_COV_ANY, GENE_CLON_ANY = 1, 2, 4     # isx_batch_profile_genes scaffold_flags bits
+
+
 ERR_CAPACITY = -3          # ISX_ERR_CAPACITY (include/instrain_amd.h)
 
 
@@ -155,6 +164,7 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_batch_create", "isx_batch_create_reads", "isx_batch_destroy", "isx_batch_run", "isx_batch_launch", "isx_batch_wait", "isx_batch_sizes", "isx_batch_timings",
            "isx_batch_fetch_entries", "isx_batch_fetch_dense", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs",
            "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
+           "isx_genes_create", "isx_genes_destroy", "isx_genes_sites", "isx_batch_profile_genes", "isx_genes_profile_snvs",
            "isx_pipe_create", "isx_pipe_destroy", "isx_pipe_submit", "isx_pipe_submit_reads", "isx_pipe_stage_reads", "isx_pipe_submit_wire", "isx_wire_bytes", "isx_wire_free", "isx_wire_keep_reference", "isx_pipe_submit_bam", "isx_encode_segs", "isx_encode_segs_ring", "isx_seg_records_needed", "isx_encode_delta", "isx_delta_records_needed", "isx_count_read_segs", "isx_pack_reads", "isx_pipe_collect", "isx_pipe_release", "isx_pipe_fetch_entries", "isx_pipe_fetch_entries_shrunk", "isx_levels_expand", "isx_encode_obs", "isx_encode_obs_ring",
            "isx_pack_ref_planes", "isx_planes_from_segs", "isx_pack_read_planes", "isx_pipe_submit_planes", "isx_pipe_stage_planes", "isx_encode_planes", "isx_encode_planes_mm", "isx_pipe_set_reference_budget", "isx_host_register", "isx_host_unregister",
            "isx_bgzf_index", "isx_bgzf_inflate_device", "isx_bgzf_inflate_host", "isx_bgzf_inflate_fast",
@@ -223,6 +233,12 @@ def load():
     lib.isx_compare_coverage.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(C.c_float)]
     lib.isx_compare_scaffolds.argtypes = [vp, vp, i32, vp, i32, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)]
     lib.isx_compare_fetch_snps.argtypes = [vp, vp]
+    lib.isx_genes_create.argtypes = [vp, i64, vp, C.c_char_p, i64, C.POINTER(vp)]
+    lib.isx_genes_destroy.argtypes = [vp]
+    lib.isx_genes_destroy.restype = None
+    lib.isx_genes_sites.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    lib.isx_batch_profile_genes.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_genes_profile_snvs.argtypes = [vp, i32, vp, vp, vp, i64, vp, i32, vp, vp, C.POINTER(C.c_float)]
     lib.isx_pipe_create.argtypes = [vp, C.POINTER(Params), C.POINTER(PipeParams), C.POINTER(vp)]
     lib.isx_pipe_destroy.argtypes = [vp]
     lib.isx_pipe_destroy.restype = None

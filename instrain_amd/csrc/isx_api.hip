@@ -1750,6 +1750,97 @@ static void fill_summary_in(isx_batch *b, int32_t n_scaffolds, const int64_t *sc
     in.n_ovf = b->n_ovf; in.ovf0 = (uint64_t)entry_wins(b) * b->slab;
 }
 
+// ---- gene profiling (isx_genes.hip) ----
+int isx_genes_create(isx_ctx *ctx, int64_t n_genes, const isx_gene *genes, const char *seq, int64_t seq_bytes, isx_genes **out)
+{
+    if (!ctx || !out || n_genes < 0 || (n_genes && !genes) || seq_bytes < 0 || (seq_bytes && !seq)) {
+        isx_set_error("isx_genes_create: bad argument");
+        return ISX_ERR_ARG;
+    }
+    *out = nullptr;
+    for (int64_t i = 0; i < n_genes; i++) {
+        const isx_gene &x = genes[i];
+        if (x.start < 0 || x.end < x.start || x.seq_off < 0 || x.seq_off + (x.end - x.start + 1) > seq_bytes || (x.strand != 1 && x.strand != -1)) {
+            isx_set_error("isx_genes_create: gene " + std::to_string(i) + " has bad coordinates, strand or sequence range");
+            return ISX_ERR_ARG;
+        }
+    }
+    std::vector<uint8_t> codes((size_t)seq_bytes);
+    for (int64_t i = 0; i < seq_bytes; i++) {
+        const char c = seq[i];
+        codes[(size_t)i] = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == 'N' ? 4 : 255;
+        if (codes[(size_t)i] == 255) { isx_set_error("isx_genes_create: gene letters must be upper-case A, C, G, T or N"); return ISX_ERR_ARG; }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    isx_genes *g = new isx_genes();
+    g->device = ctx->device; g->stream = ctx->stream;
+    g->h.assign(genes, genes + n_genes);
+    g->seq_bytes = seq_bytes;
+    hipError_t e = hipEventCreate(&g->ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&g->ev[1]);
+    if (e == hipSuccess) e = isx_raw_dev_malloc(&g->d, (size_t)std::max<int64_t>(n_genes, 1) * sizeof(isx_gene));
+    if (e == hipSuccess) e = isx_raw_dev_malloc(&g->d_seq, (size_t)std::max<int64_t>(seq_bytes, 1));
+    if (e == hipSuccess && n_genes) e = hipMemcpy(g->d, genes, (size_t)n_genes * sizeof(isx_gene), hipMemcpyHostToDevice);
+    if (e == hipSuccess && seq_bytes) e = hipMemcpy(g->d_seq, codes.data(), (size_t)seq_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        isx_set_error(std::string("isx_genes_create: ") + hipGetErrorString(e));
+        isx_genes_destroy(g);
+        return ISX_ERR_HIP;
+    }
+    *out = g;
+    return ISX_OK;
+}
+
+void isx_genes_destroy(isx_genes *g)
+{
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    if (g->d) isx_dev_free(g->d);
+    if (g->d_seq) isx_dev_free(g->d_seq);
+    for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
+    delete g;
+}
+
+int isx_genes_sites(isx_genes *g, double *sites, float *device_ms)
+{
+    if (!g || (!sites && !g->h.empty())) { isx_set_error("isx_genes_sites: bad argument"); return ISX_ERR_ARG; }
+    return run_gene_sites(g, sites, device_ms);
+}
+
+int isx_batch_profile_genes(isx_batch *b, isx_genes *g, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *gene_first,
+                            const int32_t *gene_last, isx_gene_cov *cov_out, uint8_t *scaffold_flags, float *device_ms)
+{
+    NEED_RUN(b, scaffold_flags);
+    if (!g || g->device != b->ctx->device) { isx_set_error("isx_batch_profile_genes: the gene set belongs to another device"); return ISX_ERR_ARG; }
+    if (n_scaffolds <= 0 || !scaffold_bounds || scaffold_bounds[n_scaffolds] != b->n_pos) {
+        isx_set_error("isx_batch_profile_genes: scaffold_bounds must span [0, n_pos]");
+        return ISX_ERR_ARG;
+    }
+    std::vector<GeneWork> work;
+    int rc = genes_build_work(g, n_scaffolds, scaffold_bounds, gene_first, gene_last, work);
+    if (rc) return rc;
+    if (!work.empty() && !cov_out) { isx_set_error("isx_batch_profile_genes: bad argument"); return ISX_ERR_ARG; }
+    if (b->lean && !b->d_counts && !b->d_entries) { isx_set_error("this batch lives in a lean pipe slot (isx_pipe_params.lean_output): its dense coverage / clonality arrays were not written"); return ISX_ERR_STATE; }
+    SummaryIn in{};
+    fill_summary_in(b, n_scaffolds, scaffold_bounds, in);
+    return run_gene_cov(in, b->S, work, cov_out, scaffold_flags, device_ms);
+}
+
+int isx_genes_profile_snvs(isx_genes *g, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *gene_first,
+                           const int32_t *gene_last, int64_t n_snv, const isx_snv *snv, int32_t n_levels, isx_gene_mutation *mut_out,
+                           isx_gene_snv_count *cnt_out, float *device_ms)
+{
+    if (!g || n_snv < 0 || (n_snv && (!snv || !mut_out)) || n_levels <= 0 || n_snv > 0x7FFFFFFFll) {
+        isx_set_error("isx_genes_profile_snvs: bad argument");
+        return ISX_ERR_ARG;
+    }
+    std::vector<GeneWork> work;
+    int rc = genes_build_work(g, n_scaffolds, scaffold_bounds, gene_first, gene_last, work);
+    if (rc) return rc;
+    if (!work.empty() && !cnt_out) { isx_set_error("isx_genes_profile_snvs: bad argument"); return ISX_ERR_ARG; }
+    return run_gene_snvs(g, n_scaffolds, scaffold_bounds, work, n_snv, snv, n_levels, mut_out, cnt_out, device_ms);
+}
+
 int isx_compare_coverage(isx_batch *a, isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, int32_t min_cov,
                          isx_compare_level *out, float *device_ms)
 {

@@ -1,6 +1,7 @@
 // isx_summary.h -- host-side interface of the per-scaffold summary pass (isx_summary.hip)
 #pragma once
 #include <functional>
+#include <vector>
 
 #include "isx_internal.h"
 
@@ -88,3 +89,36 @@ struct EntrySoa { uint32_t *gpos, *mm_cov; float *clon, *clon_rarefied; };
 int fetch_entries_sorted(hipStream_t s, const isx_entry *entries, const uint32_t *win_nent, uint32_t slab, uint32_t n_win,
                          uint32_t n_ovf, uint64_t n_entries, isx_entry *host_out, const EntryCopier *copier = nullptr,
                          const EntrySoa *soa = nullptr);
+
+// ---- gene profiling (isx_genes.hip; GeneProfile.py:304-707) ----
+struct isx_genes {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<isx_gene> h;            // the set as the caller gave it
+    isx_gene *d = nullptr;
+    uint8_t *d_seq = nullptr;           // the letters as codes 0..4 (A C G T N), gene orientation
+    int64_t seq_bytes = 0;
+};
+
+// one gene of a call: its interval in the call's flat space, clipped to its scaffold (fe < fs: nothing of it lies inside)
+struct GeneWork {
+    uint32_t fs, fe;                    // inclusive
+    int32_t gene;                       // index in the set
+    int32_t scaf;                       // index among the call's scaffolds
+};
+
+// the call's genes in call order (scaffold by scaffold, set order inside one), with the checks every gene entry point makes
+int genes_build_work(const isx_genes *g, int32_t n_scaffolds, const int64_t *bounds, const int32_t *first, const int32_t *last,
+                     std::vector<GeneWork> &work);
+// one level of the coverage half: rows[w * M + mm] for every call gene w (isx_genes.hip)
+void launch_gene_cov(hipStream_t s, const GeneWork *work, uint32_t n_work, const uint32_t *cov, const float *cv, int M, int mm,
+                     isx_gene_cov *rows);
+// ISX_GENE_COV_ANY / ISX_GENE_CLON_ANY of every scaffold for the current level into flags[n_seg] (zeroed by the caller)
+void launch_scaffold_any(hipStream_t s, const uint32_t *cov, const float *cv, uint32_t n_pos, const int64_t *bounds, int n_seg,
+                         uint32_t *flags);
+int run_gene_cov(const SummaryIn &in, SummaryBuffers &B, const std::vector<GeneWork> &work, isx_gene_cov *host_out,
+                 uint8_t *flags_out, float *ms);
+int run_gene_snvs(isx_genes *g, int32_t n_scaffolds, const int64_t *bounds, const std::vector<GeneWork> &work, int64_t n_snv,
+                  const isx_snv *snv, int32_t n_levels, isx_gene_mutation *mut_out, isx_gene_snv_count *cnt_out, float *ms);
+int run_gene_sites(isx_genes *g, double *sites, float *ms);

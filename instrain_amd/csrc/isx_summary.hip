@@ -751,6 +751,77 @@ int run_genome_summary(const SummaryIn &in, SummaryBuffers &B, int n_genomes, co
     return done(ISX_OK);
 }
 
+// ---- gene profiling, coverage half (GeneProfile.py:352-422): the levels are materialised as for the genome roll-up, then every
+// gene interval is reduced by one wave (isx_genes.hip k_gene_cov) and every scaffold's emptiness flags are taken ----
+namespace {
+__global__ void k_gene_flags(const uint32_t *any, const Acc *acc, int n_seg, int mm, int M, int dense, uint8_t *flags)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seg) return;
+    const uint32_t f = any[s];
+    // the dense path has a level on a scaffold when it has coverage there (as isx_batch_summarize's `present`)
+    const bool present = dense ? (f & ISX_GENE_COV_ANY) != 0 : acc[s].present != 0;
+    flags[(size_t)s * M + mm] = (uint8_t)(f | (present ? ISX_GENE_LEVEL_PRESENT : 0));
+}
+}  // namespace
+
+int run_gene_cov(const SummaryIn &in, SummaryBuffers &B, const std::vector<GeneWork> &work, isx_gene_cov *host_out,
+                 uint8_t *flags_out, float *ms)
+{
+    hipStream_t s = in.stream;
+    const uint32_t n_pos = in.n_pos;
+    const int n_scaf = in.n_scaffolds, M = in.M;
+    const size_t n_work = work.size();
+    int rc;
+    B.fit_positions(n_pos);
+    if ((rc = dev_alloc(&B.cov, B.cap_pos)) || (rc = dev_alloc(&B.cv, B.cap_pos)) || (rc = dev_alloc(&B.cr, B.cap_pos))) return rc;
+    int64_t *d_sb = nullptr;
+    GeneWork *d_work = nullptr;
+    uint32_t *d_any = nullptr;
+    Acc *d_sacc = nullptr;
+    uint8_t *d_flags = nullptr;
+    isx_gene_cov *d_rows = nullptr;
+    auto done = [&](int code) {
+        void *ps[] = {d_sb, d_work, d_any, d_sacc, d_flags, d_rows};
+        for (void *p : ps) if (p) isx_dev_free(p);
+        return code;
+    };
+#define GC_TRY(expr) do { if ((expr) != hipSuccess) { isx_set_error(std::string("HIP error in the gene coverage pass: ") + #expr); return done(ISX_ERR_HIP); } } while (0)
+    GC_TRY(isx_raw_dev_malloc(&d_sb, ((size_t)n_scaf + 1) * sizeof(int64_t)));
+    GC_TRY(isx_raw_dev_malloc(&d_work, std::max<size_t>(n_work, 1) * sizeof(GeneWork)));
+    GC_TRY(isx_raw_dev_malloc(&d_any, (size_t)n_scaf * sizeof(uint32_t)));
+    GC_TRY(isx_raw_dev_malloc(&d_sacc, (size_t)n_scaf * sizeof(Acc)));
+    GC_TRY(isx_raw_dev_malloc(&d_flags, (size_t)n_scaf * M));
+    GC_TRY(isx_raw_dev_malloc(&d_rows, std::max<size_t>(n_work * M, 1) * sizeof(isx_gene_cov)));
+    GC_TRY(hipMemcpyAsync(d_sb, in.scaffold_bounds, ((size_t)n_scaf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (n_work) GC_TRY(hipMemcpyAsync(d_work, work.data(), n_work * sizeof(GeneWork), hipMemcpyHostToDevice, s));
+    GC_TRY(hipEventRecord(in.ev[0], s));
+    const dim3 blk(256), gpos((n_pos + 255) / 256), gseg((n_scaf + 255) / 256);
+    if (M > 1) {
+        GC_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
+        GC_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cv), 0x7FC00000, n_pos, s));
+        GC_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cr), 0x7FC00000, n_pos, s));
+    }
+    for (int mm = 0; mm < M; mm++) {
+        GC_TRY(hipMemsetAsync(d_sacc, 0, (size_t)n_scaf * sizeof(Acc), s));
+        GC_TRY(hipMemsetAsync(d_any, 0, (size_t)n_scaf * sizeof(uint32_t), s));
+        if (M == 1) launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
+        else hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
+                                (uint32_t)mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
+        launch_scaffold_any(s, B.cov, B.cv, n_pos, d_sb, n_scaf, d_any);
+        launch_gene_cov(s, d_work, (uint32_t)n_work, B.cov, B.cv, M, mm, d_rows);
+        hipLaunchKernelGGL(k_gene_flags, gseg, blk, 0, s, d_any, d_sacc, n_scaf, mm, M, M == 1 ? 1 : 0, d_flags);
+    }
+    GC_TRY(hipGetLastError());
+    GC_TRY(hipEventRecord(in.ev[1], s));
+    if (n_work) GC_TRY(hipMemcpyAsync(host_out, d_rows, n_work * M * sizeof(isx_gene_cov), hipMemcpyDeviceToHost, s));
+    GC_TRY(hipMemcpyAsync(flags_out, d_flags, (size_t)n_scaf * M, hipMemcpyDeviceToHost, s));
+    GC_TRY(isx_wait_stream(s));
+#undef GC_TRY
+    if (ms) { float v = 0.f; (void)hipEventElapsedTime(&v, in.ev[0], in.ev[1]); *ms = v; }
+    return done(ISX_OK);
+}
+
 void CompareBuffers::release()
 {
     void *ps[] = {cov_a, cov_b, scratch_f, bounds, acc_a, acc_b, both, rows, keys, idx, cand, snp_rows, cursors, temp};

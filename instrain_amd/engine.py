@@ -349,9 +349,79 @@ class Batch:
                                                    out.ctypes.data, C.byref(ms)))
         return out, ms.value
 
+    def profile_genes(self, genes, scaffold_bounds, gene_first, gene_last):
+        """coverage half of the gene pass (isx_batch_profile_genes): genes [gene_first[s], gene_last[s]) of the Genes set lie on
+        scaffold s of this batch -> (GENE_COV_DT rows [n_call_genes, n_mm_bins] in call order, scaffold flags [n_scaffolds,
+        n_mm_bins] (GENE_* bits), device ms)"""
+        sb = np.ascontiguousarray(scaffold_bounds, dtype=np.int64)
+        gf = np.ascontiguousarray(gene_first, dtype=np.int32)
+        gl = np.ascontiguousarray(gene_last, dtype=np.int32)
+        n_call = int((gl - gf).sum())
+        rows = np.zeros((max(n_call, 1), self.n_mm_bins), dtype=_lib.GENE_COV_DT)
+        flags = np.zeros((len(sb) - 1, self.n_mm_bins), dtype=np.uint8)
+        ms = C.c_float(0)
+        check(self.lib.isx_batch_profile_genes(self.h, genes.h, len(sb) - 1, sb.ctypes.data, gf.ctypes.data, gl.ctypes.data,
+                                               rows.ctypes.data, flags.ctypes.data, C.byref(ms)))
+        return rows[:n_call], flags, ms.value
+
     def close(self):
         if self.h:
             self.lib.isx_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Genes:
+    """A gene set resident on the device (isx_genes_*): coordinates (0-based inclusive, scaffold coordinates), strand (+1 / -1)
+    and the genes' letters as in the .fna (gene orientation, upper-case A/C/G/T/N).  Genes of one scaffold must be consecutive."""
+
+    def __init__(self, ctx, start, end, strand, sequences):
+        self.ctx, self.lib = ctx, ctx.lib
+        n = len(sequences)
+        t = np.zeros(n, dtype=_lib.GENE_DT)
+        t["start"] = np.asarray(start, dtype=np.int64)
+        t["end"] = np.asarray(end, dtype=np.int64)
+        t["strand"] = np.asarray(strand, dtype=np.int32)
+        lens = np.array([len(s) for s in sequences], dtype=np.int64)
+        t["seq_off"] = np.concatenate([[0], np.cumsum(lens)[:-1]]) if n else np.zeros(0, np.int64)
+        blob = "".join(sequences).encode("ascii")
+        self.n = n
+        h = C.c_void_p()
+        check(self.lib.isx_genes_create(ctx.h, n, t.ctypes.data if n else None, blob, len(blob), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def sites(self):
+        """count_sites of every gene -> (float64 [n, 2] = (S_sites, N_sites), device ms)"""
+        out = np.zeros((max(self.n, 1), 2), dtype=np.float64)
+        ms = C.c_float(0)
+        check(self.lib.isx_genes_sites(self.h, out.ctypes.data, C.byref(ms)))
+        return out[:self.n], ms.value
+
+    def profile_snvs(self, scaffold_bounds, gene_first, gene_last, snv, n_levels):
+        """SNV half (isx_genes_profile_snvs) on SNV_DT rows in (gpos, mm) order -> (GENE_MUTATION_DT [n_snv],
+        GENE_SNV_COUNT_DT [n_call_genes, n_levels], device ms)"""
+        sb = np.ascontiguousarray(scaffold_bounds, dtype=np.int64)
+        gf = np.ascontiguousarray(gene_first, dtype=np.int32)
+        gl = np.ascontiguousarray(gene_last, dtype=np.int32)
+        snv = np.ascontiguousarray(snv, dtype=SNV_DT)
+        n_call = int((gl - gf).sum())
+        mut = np.zeros(max(len(snv), 1), dtype=_lib.GENE_MUTATION_DT)
+        cnt = np.zeros((max(n_call, 1), int(n_levels)), dtype=_lib.GENE_SNV_COUNT_DT)
+        ms = C.c_float(0)
+        check(self.lib.isx_genes_profile_snvs(self.h, len(sb) - 1, sb.ctypes.data, gf.ctypes.data, gl.ctypes.data, len(snv),
+                                              snv.ctypes.data if len(snv) else None, int(n_levels), mut.ctypes.data, cnt.ctypes.data,
+                                              C.byref(ms)))
+        return mut[:len(snv)], cnt[:n_call], ms.value
+
+    def close(self):
+        if self.h:
+            self.lib.isx_genes_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -21,6 +21,7 @@ import pandas as pd
 
 from .. import dist as idist
 from .. import _lib, engine
+from . import gene_profile
 from .snv_utilities import CLASSES, null_model_lut
 
 BASES = np.array(["A", "C", "T", "G", "N"])
@@ -691,6 +692,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     plus `s2s` (scaffold -> upper-cased sequence, controller.py:337), `null_model` (dict, snv_utilities.py:14-38),
     optionally `ctx` (an engine.Context to reuse), `device`, `scaffold_tables` (dict that receives every scaffold's
     cumulative_scaffold_table from the device summaries), `logs` (list that receives the failure lines),
+    `gene_file` (prodigal .fna) or `genes` ((scaff2geneinfo, scaff2gene2sequence)) with `gene_tables` (dict that receives genes_table,
+    genes_coverage, genes_clonality, genes_SNP_count and SNP_mutation_types: the gene pass, gene_profile.py, on every batch),
     `batch_positions` / `batch_reads` (size of a device batch; `batch_observations` is accepted as 150 x batch_reads), `pipe_depth` (device batches in flight: the front end
     prepares batch k + 1 while batch k is profiled and its tables are cut), `stats` (dict that receives stage times).
     The BAM's reads go to the device as read segments (isx_pipe_submit_bam on a read-level pipe): the host never expands a
@@ -727,11 +730,14 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
 
     own_ctx = kwargs.get('ctx') is None
     own_bf = kwargs.get('bamfile') is None           # a caller's handle may already hold the scan (dist.profile_bam_sharded)
-    ctx = bf = pipe = helpers = None
+    ctx = bf = pipe = helpers = gset = None
+    if kwargs.get('genes') is None and kwargs.get('gene_file'):        # a gene file the run cannot use is the caller's error, not a split's
+        kwargs['genes'] = gene_profile.parse_genes(kwargs['gene_file'])
     try:
         ctx = kwargs.get('ctx') or engine.Context(int(kwargs.get('device', 0)))
         lut, fb = null_model_lut(null_model)
         ctx.set_null_model(lut, fb)
+        gset = gene_profile.start_genes(ctx, kwargs)
         bf = kwargs.get('bamfile') or engine.BamFile(bam, threads=int(kwargs.get('host_threads', 0)))
         refs = bf.refs()
         tid_of = {n: i for i, (n, _, _) in enumerate(refs)}
@@ -921,6 +927,22 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
                         if kwargs.get('scaffold_tables') is not None:
                             snp = tables.snp_table(g.first_split[j], g.first_split[j + 1])     # the scaffold's rows in one cut
                             kwargs['scaffold_tables'][name] = make_coverage_table(levels[j], refs[plan[k][0]][1], name, snp)
+                if gset is not None and splits:             # profile_genes_from_profile of every scaffold of the batch (gene_profile.py)
+                    src = splits[0]._src[0]
+                    names = [plan[k][1] for k in g.items]
+                    sb = np.r_[0, np.cumsum([refs[tid][1] for tid in g.tids])]
+                    snv = [_parse_Sdb(_make_snp_table(src.snp_table(g.first_split[j], g.first_split[j + 1]))) for j in range(len(names))]
+                    snv = [d for d in snv if len(d)]
+                    snv = pd.concat([d.astype({'scaffold': object, 'con_base': object}) for d in snv]) if snv else pd.DataFrame()
+                    gl = []
+                    gt = gene_profile.profile_batch(res["slot"], gset, names, sb, snv, mm_values, gl)
+                    for line in gl:
+                        line = "\n{1} {0}".format(line, time.strftime('%m-%d %H:%M'))
+                        logging.error(line)
+                        if logs is not None:
+                            logs.append(line)
+                    for kk in gene_profile.TABLE_NAMES:
+                        gset.tables[kk].append(gt[kk])
             finally:
                 pipe.release(t)
                 g.ticket = None
@@ -1019,6 +1041,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
                 run_alone(items)
         while in_flight:
             drain_one()
+        if gset is not None:
+            gene_profile.finish_genes(gset, kwargs['gene_tables'] if kwargs.get('gene_tables') is not None else {})
         return out
     except Exception as e:
         # a failure of the call as a whole (unreadable BAM, a pair beyond the 128 mm levels a device batch holds, a device fault):
@@ -1037,6 +1061,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     finally:
         if helpers is not None:
             helpers.shutdown(wait=True)
+        if gset is not None:
+            gset.close()
         # this call's own large arrays (sequence codes, group layouts) go before the helper thread below starts unmapping the pipe's
         # and the handle's gigabytes: both want the process' address-space lock
         try:
