@@ -817,8 +817,10 @@ int batch_window_for(const isx_batch *b, int64_t n_pos, bool packed)
     return std::min(std::max(wmax, 64), 2 * b->block);
 }
 
-uint64_t build_window_directory(const uint32_t *cmin, const uint32_t *cmax, const uint8_t *cany, uint64_t n_chunks, int W,
-                                int64_t n_pos, std::vector<uint2> &win, uint32_t chunk)
+// window -> record range directory from the per-chunk position ranges (prefix-max / suffix-min); returns the longest record
+// range of a window
+static uint64_t build_window_directory(const uint32_t *cmin, const uint32_t *cmax, const uint8_t *cany, uint64_t n_chunks, int W,
+                                       int64_t n_pos, std::vector<uint2> &win, uint32_t chunk)
 {
     std::vector<uint32_t> pmax(n_chunks), smin(n_chunks);
     uint32_t run = 0;
@@ -842,8 +844,8 @@ uint64_t build_window_directory(const uint32_t *cmin, const uint32_t *cmax, cons
 // The same directory on a pool's threads (a pipe's submit runs it between a batch's record pass and the batch's copy-in: 0.25 ms on the
 // calling thread while the stager's threads wait, once per batch).  Two steps: running max / min per block of chunks with the blocks'
 // carries applied on access, then every thread its run of windows (binary search for the first window, two pointers after).
-uint64_t build_window_directory_mt(isxenc::HostPool &pool, const uint32_t *cmin, const uint32_t *cmax, const uint8_t *cany, uint64_t n_chunks, int W,
-                                   int64_t n_pos, std::vector<uint2> &win, uint32_t chunk, std::vector<uint32_t> &pmax, std::vector<uint32_t> &smin)
+static uint64_t build_window_directory_mt(isxenc::HostPool &pool, const uint32_t *cmin, const uint32_t *cmax, const uint8_t *cany, uint64_t n_chunks, int W,
+                                          int64_t n_pos, std::vector<uint2> &win, uint32_t chunk, std::vector<uint32_t> &pmax, std::vector<uint32_t> &smin)
 {
     const int n_win = (int)((n_pos + W - 1) / W);
     const int T = std::min(pool.size(), 16);
@@ -896,6 +898,43 @@ uint64_t build_window_directory_mt(isxenc::HostPool &pool, const uint32_t *cmin,
         }
     }
     return longest;
+}
+
+int choose_windows(const isx_batch *b, int64_t n_pos, const ChunkDir &dir, DirThreads *mt, std::vector<uint2> &win, int *packed)
+{
+    auto build = [&](int W) {
+        return mt ? build_window_directory_mt(mt->pool, dir.cmin, dir.cmax, dir.cany, dir.n_chunks, W, n_pos, win, dir.chunk, mt->pmax, mt->smin)
+                  : build_window_directory(dir.cmin, dir.cmax, dir.cany, dir.n_chunks, W, n_pos, win, dir.chunk);
+    };
+    *packed = 0;
+    if ((b->M > 1 || b->drec) && !(b->prm.layout & ISX_LAYOUT_NO_PACKED_COUNTERS)) {
+        // u16-packed counters are legal when no window streams >= 65536 records (reference-delta records: 32768 -- a
+        // coverage difference is signed)
+        const int Wp = batch_window_for(b, n_pos, true);
+        if (build(Wp) < (b->drec ? 32768u : 65536u)) { *packed = 1; return Wp; }
+    }
+    const int W = batch_window_for(b, n_pos, false);
+    build(W);
+    return W;
+}
+
+int check_split_bounds(int64_t n_pos, int32_t n_splits, const int64_t *split_bounds)
+{
+    if (split_bounds[0] != 0 || split_bounds[n_splits] != n_pos) { isx_set_error("split_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
+    for (int i = 0; i < n_splits; i++)
+        if (split_bounds[i + 1] <= split_bounds[i]) { isx_set_error("split_bounds must be strictly ascending"); return ISX_ERR_ARG; }
+    return ISX_OK;
+}
+
+int seg_status_error(int erc, const char *capacity_text, int capacity_code)
+{
+    switch (erc) {
+    case isxenc::SEG_OK: return ISX_OK;
+    case isxenc::SEG_CAPACITY: isx_set_error(capacity_text); return capacity_code;
+    case isxenc::SEG_MM_RANGE: isx_set_error("a segment has mm >= n_mm_bins"); return ISX_ERR_MM_RANGE;
+    case isxenc::SEG_BAD_POS: isx_set_error("a segment reaches beyond n_pos"); return ISX_ERR_ARG;
+    default: isx_set_error("a segment's length is not in [1, 150]"); return ISX_ERR_ARG;
+    }
 }
 
 int batch_set_geometry(isx_batch *b)
@@ -1099,9 +1138,7 @@ static int batch_create_impl(isx_ctx *c, const isx_params *prm, int64_t n_pos, c
     if (prm->n_mm_bins < 1 || prm->n_mm_bins > 128) { isx_set_error("n_mm_bins must be in [1, 128]"); return ISX_ERR_ARG; }
     if (prm->enable_linkage && prm->linkage_mode == 2 && prm->n_mm_bins != 1) { isx_set_error("the dense MFMA linkage path needs n_mm_bins == 1"); return ISX_ERR_ARG; }
     if (n_pos >= (int64_t)0xFFFF0000ll) { isx_set_error("flat position space must be < 2^32 - 65536"); return ISX_ERR_ARG; }
-    if (split_bounds[0] != 0 || split_bounds[n_splits] != n_pos) { isx_set_error("split_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
-    for (int i = 0; i < n_splits; i++)
-        if (split_bounds[i + 1] <= split_bounds[i]) { isx_set_error("split_bounds must be strictly ascending"); return ISX_ERR_ARG; }
+    { const int brc = check_split_bounds(n_pos, n_splits, split_bounds); if (brc != ISX_OK) return brc; }
     HIP_TRY(hipSetDevice(c->device));
 
     isx_batch *b = new isx_batch();
@@ -1181,13 +1218,7 @@ static int batch_create_impl(isx_ctx *c, const isx_params *prm, int64_t n_pos, c
             J.cmin = st.cmin.data(); J.cmax = st.cmax.data(); J.cany = st.cany.data(); J.cap_rec = cap_rec;
             const int erc = isxenc::encode_delta(pool, J);
             if (erc == isxenc::SEG_CAPACITY && J.need_slack > slack && attempt == 0) { exact = J.task_need; continue; }
-            if (erc != isxenc::SEG_OK) {
-                isx_batch_destroy(b);
-                if (erc == isxenc::SEG_MM_RANGE) { isx_set_error("a segment has mm >= n_mm_bins"); return ISX_ERR_MM_RANGE; }
-                isx_set_error(erc == isxenc::SEG_BAD_POS ? "a segment reaches beyond n_pos" : erc == isxenc::SEG_BAD_LEN ? "a segment's length is not in [1, 150]"
-                                                                                           : "internal: segment stream larger than estimated");
-                return erc == isxenc::SEG_CAPACITY ? ISX_ERR_STATE : ISX_ERR_ARG;
-            }
+            if (erc != isxenc::SEG_OK) { isx_batch_destroy(b); return seg_status_error(erc, "internal: segment stream larger than estimated", ISX_ERR_STATE); }
             break;
         }
         b->n_rec = (uint64_t)J.n_rec;
@@ -1217,13 +1248,7 @@ static int batch_create_impl(isx_ctx *c, const isx_params *prm, int64_t n_pos, c
         J.rec = h_rec.data(); J.gbase = h_gbase.data(); J.pair_out = prm->enable_linkage ? h_pair.data() : nullptr;
         J.cmin = st.cmin.data(); J.cmax = st.cmax.data(); J.cany = st.cany.data(); J.cap_rec = cap_rec;
         const int erc = isxenc::encode_segs(pool, J);
-        if (erc != isxenc::SEG_OK) {
-            isx_batch_destroy(b);
-            if (erc == isxenc::SEG_MM_RANGE) { isx_set_error("a segment has mm >= n_mm_bins"); return ISX_ERR_MM_RANGE; }
-            isx_set_error(erc == isxenc::SEG_BAD_POS ? "a segment reaches beyond n_pos" : erc == isxenc::SEG_BAD_LEN ? "a segment's length is not in [1, 150]"
-                                                                                       : "internal: segment stream larger than estimated");
-            return erc == isxenc::SEG_CAPACITY ? ISX_ERR_STATE : ISX_ERR_ARG;
-        }
+        if (erc != isxenc::SEG_OK) { isx_batch_destroy(b); return seg_status_error(erc, "internal: segment stream larger than estimated", ISX_ERR_STATE); }
         b->n_rec = (uint64_t)J.n_rec;
         b->n_pairs = (uint64_t)J.max_pair + 1;
         st.n_chunks = b->n_rec / ISX_SEG_GROUP;
@@ -1253,17 +1278,7 @@ static int batch_create_impl(isx_ctx *c, const isx_params *prm, int64_t n_pos, c
     // ---- window -> record range: prefix-max / suffix-min over the chunk directory ----
     {
         std::vector<uint2> win;
-        b->packed = 0;
-        int W = batch_window_for(b, n_pos, false);
-        if (!dense || b->drec) {
-            // u16-packed counters are legal when no window streams >= 65536 records (reference-delta records: 32768 -- a
-            // coverage difference is signed)
-            const int Wp = batch_window_for(b, n_pos, true);
-            if (!(prm->layout & ISX_LAYOUT_NO_PACKED_COUNTERS) &&
-                build_window_directory(cmin.data(), cmax.data(), cany.data(), n_chunks, Wp, n_pos, win, dir_chunk) < (b->drec ? 32768u : 65536u)) { b->packed = 1; W = Wp; }
-        }
-        if (!b->packed) build_window_directory(cmin.data(), cmax.data(), cany.data(), n_chunks, W, n_pos, win, dir_chunk);
-        b->W = W;
+        b->W = choose_windows(b, n_pos, ChunkDir{cmin.data(), cmax.data(), cany.data(), n_chunks, dir_chunk}, nullptr, win, &b->packed);
         b->n_win = (int)win.size();
         BT(batch_set_geometry(b));
         if (!dense) {

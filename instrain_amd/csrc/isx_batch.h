@@ -153,12 +153,21 @@ std::vector<uint16_t> build_thresholds(const std::vector<int32_t> &lut, int32_t 
 void batch_pick_block(isx_batch *b);
 int batch_window_for(const isx_batch *b, int64_t n_pos, bool packed);
 
-// window -> record range directory from the per-chunk position ranges (prefix-max / suffix-min); returns
-// the longest record range of a window
-uint64_t build_window_directory(const uint32_t *cmin, const uint32_t *cmax, const uint8_t *cany, uint64_t n_chunks, int W,
-                                int64_t n_pos, std::vector<uint2> &win, uint32_t chunk = ISX_CHUNK);
-uint64_t build_window_directory_mt(isxenc::HostPool &pool, const uint32_t *cmin, const uint32_t *cmax, const uint8_t *cany, uint64_t n_chunks, int W,
-                                   int64_t n_pos, std::vector<uint2> &win, uint32_t chunk, std::vector<uint32_t> &pmax, std::vector<uint32_t> &smin);
+// split_bounds of a batch must span [0, n_pos] and ascend strictly (the one-shot batch and every form of the pipe's submit)
+int check_split_bounds(int64_t n_pos, int32_t n_splits, const int64_t *split_bounds);
+
+// a segment encoder's status (isxenc::SEG_*) as the caller's error: text set, code returned (SEG_OK: ISX_OK, nothing set).  What
+// SEG_CAPACITY means depends on who sized the record region, so its text and code are the caller's.
+int seg_status_error(int erc, const char *capacity_text, int capacity_code);
+
+// the per-chunk position ranges an encoder leaves behind: chunk i holds records [i * chunk, (i + 1) * chunk)
+struct ChunkDir { const uint32_t *cmin, *cmax; const uint8_t *cany; uint64_t n_chunks; uint32_t chunk; };
+// the directory built on a pool's threads, with the caller's scratch (a pipe's slot keeps it from batch to batch)
+struct DirThreads { isxenc::HostPool &pool; std::vector<uint32_t> &pmax, &smin; };
+// The window of a batch of n_pos positions and its window -> record range directory (`win`): the packed window when the batch's
+// format allows 16-bit counters and no window streams too many records for them, else the plain one.  Returns W, sets *packed.
+// mt == nullptr: built on the calling thread.
+int choose_windows(const isx_batch *b, int64_t n_pos, const ChunkDir &dir, DirThreads *mt, std::vector<uint2> &win, int *packed);
 
 // derived launch geometry (LDS bytes, persistent grid, row-queue capacity, entry slab) once b->W / b->packed are set
 int batch_set_geometry(isx_batch *b);

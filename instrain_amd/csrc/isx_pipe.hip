@@ -62,6 +62,7 @@ void host_block_free(void *p, bool pinned)
     if (pinned) isx_pin_free(p); else free(p);
 }
 
+static const bool pipe_timing = getenv("ISX_PIPE_TIMING") != nullptr;     // tuning aid (stderr only), set from outside the process: read once
 #define H2D(p, s) ((s).h2d ? (s).h2d : (p)->s_h2d)
 struct Slot {
     isx_batch *b = nullptr;
@@ -143,13 +144,9 @@ static uint64_t bytes_checksum(const void *p, size_t bytes, uint64_t seed)
 // The reference codes of a batch as they travel and lie in a slot: a 2-bit plane (A C T G; anything else as 0), four positions a
 // byte, and -- only when the batch holds a position that is not A/C/T/G -- a bit plane marking those (PileupArgs::ref_packed == 2,
 // ref_n).  0.25 (0.375) bytes a position over PCIe instead of 0.5 (round 3's nibbles) or 1.  plane2 holds (n_pos + 3) / 4 bytes,
-// nplane (n_pos + 7) / 8; returns whether the N plane is needed (it is always written).
+// nplane (n_pos + 7) / 8; isxenc::pack_ref_planes makes them of the codes and returns whether the N plane is needed (it is always written).
 static inline size_t ref2_bytes(int64_t n_pos) { return (((size_t)n_pos + 3) / 4 + 15) & ~(size_t)15; }
 static inline size_t refn_bytes(int64_t n_pos) { return (((size_t)n_pos + 7) / 8 + 15) & ~(size_t)15; }
-static bool pack_ref2(isxenc::HostPool &pool, const uint8_t *ref, int64_t n_pos, uint8_t *plane2, uint8_t *nplane)
-{
-    return isxenc::pack_ref_planes(pool, ref, n_pos, plane2, nplane);
-}
 
 // the caller's own planes into staging (isx_ref_planes): a copy on the pool's threads; returns whether the N plane marks a position
 static bool copy_ref_planes(isxenc::HostPool &pool, const isx_ref_planes *rp, int64_t n_pos, uint8_t *plane2, uint8_t *nplane)
@@ -373,7 +370,7 @@ static void pipe_free(isx_pipe *p)
         t_pin += now_ms() - t_x;
         for (hipEvent_t e : {s.ev_h2d0, s.ev_h2d1, s.ev_pass, s.ev_d2h0, s.ev_d2h1, s.ev_h2da, s.ev_h2db}) if (e) (void)hipEventDestroy(e);
     }
-    if (getenv("ISX_PIPE_TIMING"))      // tuning aid (stderr only)
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe_destroy] device tables %.1f ms, device arena %.1f ms, pinned staging %.1f ms, total %.1f ms\n", t_batch, t_dev, t_pin, now_ms() - t_f0);
     for (auto &kv : p->ref_cache) { if (kv.second.d) isx_dev_free(kv.second.d); if (kv.second.ready) (void)hipEventDestroy(kv.second.ready); }
     for (int i = 0; i < 2; i++) {
@@ -500,7 +497,7 @@ static int slot_batch_create(isx_pipe *p, Slot &s, int index)
     HIP_TRY(isx_pin_malloc(reinterpret_cast<void **>(&s.h_in), host_bytes));
     const double t_a1 = now_ms();
     HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.d_in), s.in_bytes));
-    if (getenv("ISX_PIPE_TIMING"))
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe_create] slot %d: device tables %.1f ms, pinned input %.1f MB %.1f ms, device arena %.1f MB %.1f ms\n", index,
                 t_a0 - t_s0, host_bytes / 1e6, t_a1 - t_a0, s.in_bytes / 1e6, now_ms() - t_a1);
     if (prm->enable_linkage && !p->segs) {
@@ -545,7 +542,7 @@ static int slot_batch_create(isx_pipe *p, Slot &s, int index)
     // A deep pipe (a long stream of batches) amortises the pinning and keeps its copy-out fully asynchronous.
     s.out_pinned = s.out_bytes <= ((size_t)64 << 20) || p->pp.depth > 2;
     { const int hrc = host_block_alloc(reinterpret_cast<void **>(&s.h_out), s.out_bytes, s.out_pinned); if (hrc != ISX_OK) return hrc; }
-    if (getenv("ISX_PIPE_TIMING")) fprintf(stderr, "[isx_pipe_create] slot %d: %s results %.1f MB %.1f ms\n", index, s.out_pinned ? "pinned" : "pageable", s.out_bytes / 1e6, now_ms() - t_o0);
+    if (pipe_timing) fprintf(stderr, "[isx_pipe_create] slot %d: %s results %.1f MB %.1f ms\n", index, s.out_pinned ? "pinned" : "pageable", s.out_bytes / 1e6, now_ms() - t_o0);
     for (hipEvent_t *e : {&s.ev_h2d0, &s.ev_h2d1, &s.ev_pass, &s.ev_d2h0, &s.ev_d2h1, &s.ev_h2da, &s.ev_h2db}) HIP_TRY(hipEventCreate(e));
     const size_t n_chunks = (size_t)(p->cap_rec / (p->segs ? (int64_t)p->G : (int64_t)ISX_CHUNK)) + 2;
     s.cmin.resize(n_chunks); s.cmax.resize(n_chunks); s.cany.resize(n_chunks);
@@ -772,7 +769,7 @@ static int finish_slot(isx_pipe *p, Slot &s, hipStream_t sfin)
         else if (!s.ld_rows.empty()) { const int rc = pull(s.ld_rows.data(), b->L.ld.p, s.ld_rows.size() * sizeof(isx_ld)); if (rc != ISX_OK) return rc; }
     }
     s.rows_checksum = bytes_checksum(s.ld_rows.data(), p->prm.enable_linkage ? s.ld_rows.size() * sizeof(isx_ld) : 0, bytes_checksum(rows, n_snv * sizeof(isx_snv), 0));
-    if (getenv("ISX_PIPE_TIMING"))      // tuning aid (stderr only)
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe finisher] wait %.2f ms, finish (sizes, linkage) %.2f ms [device: sites %.2f allele %.2f group %.2f incr %.2f ld %.2f; %lld ao, %lld incr, %lld ld], clonTR list (%u) %.2f ms, snv rows (%zu) %.2f ms\n",
                 s.finish_wait_ms, t_fin - t_c0, b->tim.sites_ms, b->tim.allele_ms, b->tim.group_ms, b->tim.incr_ms, b->tim.ld_ms,
                 (long long)b->sizes.n_allele_obs, (long long)b->sizes.n_increments, (long long)b->sizes.n_ld, b->n_rare, t_rare - t_fin, n_snv, now_ms() - t_rare);
@@ -967,7 +964,7 @@ int isx_pipe_create(isx_ctx *c, const isx_params *prm, const isx_pipe_params *pp
             p->more_finishers.emplace_back(finisher_main, p, st);
         }
     }
-    if (getenv("ISX_PIPE_TIMING"))      // tuning aid (stderr only)
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe_create] thread pool %.1f ms, %d slot(s) %.1f ms\n", t_c1 - t_c0, pp->depth, now_ms() - t_c1);
     if (pp->stage_async && p->segs) p->stager = std::thread(stager_main, p);
     *out = p;
@@ -1059,57 +1056,277 @@ static int enqueue_pass_impl(isx_pipe *p, Slot &s, int64_t n_pos, int64_t *ticke
     return ISX_OK;
 }
 
+// ---- what every form of a submit shares ----
+// A batch reaches a slot as observation records (submit_common), as read segments / bit planes (submit_segs_common) or staged ahead of
+// time (stage_common + isx_pipe_submit_wire).  Each is the same sequence: acquire a slot; encode; stage the reference; choose the
+// windows; shape the pass; bind the slot's arenas; copy in; enqueue the pass.  Only the encoding, the reference's way to the device and
+// the copy-in differ; the other steps exist once, so that a staged, a submitted and a one-shot batch cannot come to different forms.
+
+// a batch within what the pipe was created for: positions, splits and its items (observations, or read segments)
+static int check_capacity(const isx_pipe *p, const char *who, int64_t n_pos, int64_t n_items, int64_t max_items, int32_t n_splits)
+{
+    if (n_pos > p->pp.max_pos || n_items > max_items || n_splits > p->pp.max_splits) {
+        isx_set_error(std::string(who) + ": batch larger than the pipe was created for");
+        return ISX_ERR_CAPACITY;
+    }
+    return ISX_OK;
+}
+
+// the slot of the next ticket, which must be free; the calling thread is bound to the pipe's device
+static int slot_acquire(isx_pipe *p, const char *who, Slot **out)
+{
+    Slot &s = p->slots[(size_t)(p->next_ticket % (int64_t)p->slots.size())];
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (s.state != 0) { isx_set_error(std::string(who) + ": every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
+    }
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    *out = &s;
+    return ISX_OK;
+}
+
+// a batch for the stager thread (isx_pipe_params.stage_async): it gets the next promised ticket and waits in the queue.  Only what can
+// be said without touching the reads is checked here, the rest comes back through isx_pipe_collect.  The caller's arrays stay its own
+// and unchanged until that call (or isx_pipe_release).
+static int queue_for_stager(isx_pipe *p, isx_pipe::StageJob &&job, const char *who, int64_t *ticket)
+{
+    const int rc = check_capacity(p, who, job.n_pos, job.planes ? job.reads.n_seg : job.segs.n_seg, p->pp.max_segs, (int32_t)job.bounds.size() - 1);
+    if (rc != ISX_OK) return rc;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        const int64_t t = p->next_promise, n = (int64_t)p->slots.size();
+        const Slot &s = p->slots[(size_t)(t % n)];
+        // the slot is free when the batch that had it last (ticket t - n) was staged, finished and released
+        if (t - n >= p->next_ticket || s.state != 0) { isx_set_error(std::string(who) + ": every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
+        job.ticket = t;
+        p->next_promise = t + 1;
+        *ticket = t;
+        p->stage_q.push_back(std::move(job));
+    }
+    p->cv_stage.notify_one();
+    return ISX_OK;
+}
+
+// The staging ring (isx_pipe::ring_half > 0): the pinned arena holds two halves instead of the whole record stream.  The encoder fills
+// them wave by wave, and every finished wave leaves for its place in the device arena while the next one is written into the other half.
+// `err`: the first failed wait / copy (the encoder's callbacks cannot return one); `bytes`: what the waves of the last layout carried.
+struct RingFeed { hipError_t err = hipSuccess; size_t bytes = 0; };
+
+// installs the ring on an encoder job (its ring_groups / wave_begin / wave_flush); the copy-in queue starts here.  Nothing to do in a
+// pipe without a ring.  `r` must outlive the encoding.
+static int ring_feed_install(isx_pipe *p, Slot &s, RingFeed &r, int64_t &ring_groups, std::function<void(int)> &wave_begin,
+                             std::function<void(int, int64_t, int64_t)> &wave_flush)
+{
+    if (p->ring_half <= 0) return ISX_OK;
+    HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
+    const size_t half_bytes = (size_t)p->ring_half * (size_t)p->rb, grp_bytes = (size_t)p->G * (size_t)p->rb;
+    uint8_t *d_rec = s.d_in + s.off_rec;
+    ring_groups = p->ring_half / (int64_t)p->G;
+    wave_begin = [&s, &r](int h) {
+        if (s.ring_busy[h]) { const hipError_t e = isx_wait_event(s.ev_ring[h]); if (e != hipSuccess && r.err == hipSuccess) r.err = e; s.ring_busy[h] = false; }
+    };
+    wave_flush = [p, &s, &r, half_bytes, grp_bytes, d_rec](int h, int64_t g0, int64_t g1) {
+        const size_t n = (size_t)(g1 - g0) * grp_bytes;
+        // the observation encoder writes a layout that overflowed again from the start, inside one call: the count starts over at group 0
+        // (the segment encoders' waves only ascend and submit resets the count before every attempt: for them this changes nothing)
+        if (g0 == 0) r.bytes = 0;
+        hipError_t e = hipMemcpyAsync(d_rec + (size_t)g0 * grp_bytes, s.h_in + s.off_rec + (size_t)h * half_bytes, n, hipMemcpyHostToDevice, H2D(p, s));
+        if (e == hipSuccess) e = hipEventRecord(s.ev_ring[h], H2D(p, s));
+        if (e != hipSuccess && r.err == hipSuccess) r.err = e;
+        s.ring_busy[h] = true;
+        r.bytes += n;
+    };
+    return ISX_OK;
+}
+
+// The window of the batch in slot `s` (b->n_pos / n_rec set) and its directory, into the slot's staging.  `chunk`: records per entry of
+// the chunk directory the encoder left in the slot -- the observation encoder writes one per ISX_CHUNK records whatever the record
+// size, the segment encoders one per group (p->G).  threads: built on the pool (the read-level forms; the observation form has always
+// built it on the calling thread: same directory either way, choose_windows).
+static int slot_choose_windows(isx_pipe *p, Slot &s, uint32_t chunk, bool threads)
+{
+    isx_batch *b = s.b;
+    DirThreads mt{*p->pool, s.dir_pmax, s.dir_smin};
+    const ChunkDir dir{s.cmin.data(), s.cmax.data(), s.cany.data(), b->n_rec / chunk, chunk};
+    b->W = choose_windows(b, b->n_pos, dir, threads ? &mt : nullptr, s.win, &b->packed);
+    b->n_win = (int)s.win.size();
+    if (s.win.size() > (size_t)p->pp.max_pos / 64 + 2) { isx_set_error("internal: window directory larger than the arena"); return ISX_ERR_STATE; }
+    memcpy(s.h_in + s.off_win, s.win.data(), s.win.size() * sizeof(uint2));
+    return ISX_OK;
+}
+
+// What a pass hands back depends on the batch's mean depth (n_obs / n_pos); a staged and a submitted batch must come to the same form
+// (the tests compare them byte for byte), so the cuts live here alone.
+constexpr double COV8_BELOW_DEPTH = 16.0;       // coverage travels in one byte a position
+constexpr double NIB_BELOW_DEPTH = 6.0;         // lean slots: ... in four bits (most windows stay within them)
+constexpr double LEV_COV8_BELOW_DEPTH = 64.0;   // level-sparse slots: a level's coverage in one byte (the few values >= 255 travel in a list)
+constexpr double RARE_DENSE_OBS_FACTOR = 4.0;   // lean slots: the clonTR table goes back dense once n_obs * 4 >= rarefied_coverage * n_pos
+
+// The output form of the pass over the batch in slot `s`, its launch geometry and entry slabs: b->n_pos / n_obs and the window choice
+// (b->W / packed / n_win: slot_choose_windows, or a wire's stored choice) are set.
+static int slot_shape_pass(isx_pipe *p, Slot &s)
+{
+    isx_batch *b = s.b;
+    const bool dense = b->M == 1;
+    const double n_obs = (double)b->n_obs, n_pos = (double)b->n_pos;
+    // without a count table to hand back, the position-sized tables travel shrunk (see finish_slot): clonality as the list of
+    // values other than 1.0, coverage in one byte for a shallow batch
+    b->sparse_out = dense && b->d_clon_list != nullptr;
+    b->cov8_out = b->sparse_out && n_obs < COV8_BELOW_DEPTH * n_pos;
+    b->nib_out = b->cov8_out && b->lean && n_obs < NIB_BELOW_DEPTH * n_pos;
+    b->clon_dense = false;
+    b->rare_dense = !(b->lean && b->sparse_out) || n_obs * RARE_DENSE_OBS_FACTOR >= (double)p->prm.rarefied_coverage * n_pos;
+    if (b->lev_sparse) b->lev_cov_bytes = n_obs < LEV_COV8_BELOW_DEPTH * n_pos ? 1 : 2;
+    const int rc = batch_set_geometry(b);
+    if (rc != ISX_OK) return rc;
+    if (!dense && !b->lev_sparse) {
+        const size_t used = (size_t)b->n_win * b->slab;
+        if (used > b->slab_region) { isx_set_error("internal: entry slabs larger than the slot's region"); return ISX_ERR_STATE; }
+        b->cap_ovf = b->cap_entries - used;
+    }
+    return ISX_OK;
+}
+
+// the slot's device arenas as the batch's inputs; the pipe's record format says which stream pointer is the live one.
+// resident_ref: the reference planes already lie elsewhere on the device (a keyed reference, a wire's kept one), else nullptr
+static void slot_bind_inputs(isx_pipe *p, Slot &s, uint8_t *resident_ref)
+{
+    isx_batch *b = s.b;
+    const bool linkage = p->prm.enable_linkage != 0;
+    uint8_t *rec = s.d_in + s.off_rec;
+    b->d_bounds = reinterpret_cast<int64_t *>(s.d_in + s.off_bounds);
+    b->d_win = reinterpret_cast<uint2 *>(s.d_in + s.off_win);
+    b->d_ref = resident_ref ? resident_ref : s.d_in + s.off_ref;
+    b->d_ref_n = s.ref_has_n ? b->d_ref + ref2_bytes(b->n_pos) : nullptr;
+    b->d_gbase = reinterpret_cast<uint32_t *>(s.d_in + s.off_gbase);
+    b->d_rec16 = p->rb == 2 ? reinterpret_cast<uint16_t *>(rec) : nullptr;
+    b->d_rec32 = p->rb == 4 ? reinterpret_cast<uint32_t *>(rec) : nullptr;
+    if (p->segs) {          // read-level: one pair id per record (reference-delta records carry the ids themselves), no run tables
+        b->d_seg = p->drec ? nullptr : reinterpret_cast<uint4 *>(rec);
+        b->d_drec = p->drec ? reinterpret_cast<uint4 *>(rec) : nullptr;
+        b->d_pair = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.d_in + s.off_pairs) : nullptr;
+        b->d_pair_runs = nullptr; b->d_run_index = nullptr; b->n_runs = 0;
+    } else {                // observation records: pair-id runs + their index (b->n_runs is the encoder's count)
+        b->d_pair = nullptr;
+        b->d_pair_runs = linkage ? s.d_runs : nullptr;
+        b->d_run_index = linkage ? reinterpret_cast<uint32_t *>(s.d_in + s.off_ridx) : nullptr;
+        b->d_gpos16 = s.d_gpos16; b->gpos16_shift = 5;
+    }
+}
+
+// first trip of a reference key: a device-side copy of the planes that just arrived in the slot stays with the pipe (while its budget
+// lasts).  No entry when it cannot be made: the batch goes on with the planes that travelled, nothing leaks.
+static void ref_cache_insert(isx_pipe *p, Slot &s, const isx_ref_planes *rp, int64_t n_pos)
+{
+    const size_t rb_all = ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0);
+    if (p->ref_cache_bytes + rb_all > p->ref_cache_budget.load(std::memory_order_relaxed)) return;
+    isx_pipe::RefEntry e;
+    bool ok = isx_dev_malloc(reinterpret_cast<void **>(&e.d), rb_all + 64) == hipSuccess && hipEventCreateWithFlags(&e.ready, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipMemcpyAsync(e.d, s.d_in + s.off_ref, rb_all, hipMemcpyDeviceToDevice, H2D(p, s)) == hipSuccess && hipEventRecord(e.ready, H2D(p, s)) == hipSuccess;
+    if (ok) {
+        e.bytes = rb_all; e.n_pos = n_pos; e.has_n = s.ref_has_n; e.sum = ref_plane_checksum(rp->plane2, n_pos);
+        p->ref_cache_bytes += rb_all;
+        p->ref_cache.emplace(rp->key, e);
+    } else {
+        if (e.d) isx_dev_free(e.d);
+        if (e.ready) (void)hipEventDestroy(e.ready);
+        (void)hipGetLastError();
+    }
+}
+
+// how the reference planes of a bit-plane batch got on their way (stage_reference)
+struct RefStage {
+    bool early = false;                 // they left (or lie on the device already): the copy-in skips them
+    uint8_t *resident = nullptr;        // the planes on the device outside the slot's arena (isx_ref_planes.key)
+    double host_ms = 0.0;               // this step's own host time (ISX_PIPE_TIMING)
+};
+
+// The reference planes of a bit-plane batch, BEFORE its records are made: the record pass compares the reads against a host-side copy
+// (J.ref2 / J.refn are set to it), and the planes leave at once so that the copy engine brings them in while the threads encode.
+// They travel in one of three ways; sets s.ref_has_n.  `rp`: the caller's planes, nullptr: packed from the codes `ref`.
+static int stage_reference(isx_pipe *p, Slot &s, int64_t n_pos, const uint8_t *ref, const isx_ref_planes *rp, isxenc::SegJob &J, RefStage *out)
+{
+    const bool ring = p->ring_half > 0;         // (the ring recorded ev_h2d0 when it was installed)
+    const double t_r = now_ms();
+    const size_t b2 = ((size_t)n_pos + 3) / 4, bn = ((size_t)n_pos + 7) / 8;
+    hipStream_t st = H2D(p, s);
+
+    // 1. resident under the caller's key: nothing is staged, nothing travels; the record pass compares against the caller's own planes
+    const auto hit = rp && rp->key ? p->ref_cache.find(rp->key) : p->ref_cache.end();
+    if (hit != p->ref_cache.end()) {
+        const isx_pipe::RefEntry &e = hit->second;
+        if (e.n_pos != n_pos || e.has_n != (rp->nplane != nullptr && e.has_n) || e.sum != ref_plane_checksum(rp->plane2, n_pos)) {
+            isx_set_error("isx_pipe_submit_planes: the reference key stands for other planes (positions / non-ACGT plane / content differ)");
+            return ISX_ERR_ARG;
+        }
+        s.ref_has_n = e.has_n;
+        J.ref2 = rp->plane2; J.refn = e.has_n ? rp->nplane : nullptr;
+        out->resident = e.d;
+        HIP_TRY(hipStreamWaitEvent(st, e.ready, 0));            // (the entry's own copy, enqueued by an earlier submit)
+        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, st));
+        HIP_TRY(hipEventRecord(s.ev_h2da, st));
+        out->early = true;
+        out->host_ms = now_ms() - t_r;
+        return ISX_OK;
+    }
+
+    // 2. the caller's planes are registered for the copy engine (isx_host_register): they leave from where they lie, nothing is staged,
+    // the record pass compares against them.  (A key's FIRST trip still goes through staging: its device copy is made of that.)
+    const bool first_trip = rp && rp->key && p->ref_cache_budget.load(std::memory_order_relaxed) > 0;
+    if (rp && !first_trip && isx_host_is_registered(rp->plane2, b2) && (!rp->nplane || isx_host_is_registered(rp->nplane, bn))) {
+        const bool any_n = rp->nplane && plane_any(*p->pool, rp->nplane, bn);
+        s.ref_has_n = any_n;
+        J.ref2 = rp->plane2; J.refn = any_n ? rp->nplane : nullptr;
+        out->host_ms = now_ms() - t_r;
+        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, st));
+        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, rp->plane2, b2, hipMemcpyHostToDevice, st));
+        if (any_n) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref + ref2_bytes(n_pos), rp->nplane, bn, hipMemcpyHostToDevice, st));
+        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2da, st));
+        out->early = true;
+        return ISX_OK;
+    }
+
+    // 3. through the slot's staging: the caller's planes copied, or the codes packed
+    uint8_t *h2 = s.h_in + s.off_ref, *hn = h2 + ref2_bytes(n_pos);
+    s.ref_has_n = rp ? copy_ref_planes(*p->pool, rp, n_pos, h2, hn) : isxenc::pack_ref_planes(*p->pool, ref, n_pos, h2, hn);
+    J.ref2 = h2; J.refn = s.ref_has_n ? hn : nullptr;
+    out->host_ms = now_ms() - t_r;
+    // (ISX_PIPE_LATE_DMA=1: every copy after the host pass, as before round 5 -- same-box A/B)
+    static const bool late_dma = getenv("ISX_PIPE_LATE_DMA") != nullptr;
+    if (late_dma) return ISX_OK;
+    if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, st));
+    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, h2, ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0), hipMemcpyHostToDevice, st));
+    if (!ring) HIP_TRY(hipEventRecord(s.ev_h2da, st));
+    out->early = true;
+    if (rp && rp->key) ref_cache_insert(p, s, rp, n_pos);
+    return ISX_OK;
+}
+
 // the common part of a submit: `J` arrives with its input side set (arrays, or a producer), everything else happens here
 static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t n_splits, const int64_t *split_bounds,
                          int64_t n_obs, isxenc::EncodeJob &J, int64_t *ticket)
 {
-    if (n_pos > p->pp.max_pos || n_obs > p->pp.max_obs || n_splits > p->pp.max_splits) {
-        isx_set_error("isx_pipe_submit: batch larger than the pipe was created for");
-        return ISX_ERR_CAPACITY;
-    }
-    if (split_bounds[0] != 0 || split_bounds[n_splits] != n_pos) { isx_set_error("split_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
-    for (int i = 0; i < n_splits; i++)
-        if (split_bounds[i + 1] <= split_bounds[i]) { isx_set_error("split_bounds must be strictly ascending"); return ISX_ERR_ARG; }
-    Slot &s = p->slots[(size_t)(p->next_ticket % (int64_t)p->slots.size())];
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (s.state != 0) { isx_set_error("isx_pipe_submit: every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
-    }
-    isx_ctx *c = p->ctx;
+    static const char who[] = "isx_pipe_submit";
+    int rc;
+    if ((rc = check_capacity(p, who, n_pos, n_obs, p->pp.max_obs, n_splits)) != ISX_OK) return rc;
+    if ((rc = check_split_bounds(n_pos, n_splits, split_bounds)) != ISX_OK) return rc;
+    Slot *slot = nullptr;
+    if ((rc = slot_acquire(p, who, &slot)) != ISX_OK) return rc;
+    Slot &s = *slot;
     isx_batch *b = s.b;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool dense = b->M == 1, linkage = p->prm.enable_linkage != 0;
+    const bool linkage = p->prm.enable_linkage != 0;
 
     // ---- host threads: records + group bases (+ pair-id runs) into pinned staging, reference codes, bounds ----
     const double t0 = now_ms();
     const bool ring = p->ring_half > 0;
     uint8_t *d_rec = s.d_in + s.off_rec;
-    hipError_t ring_err = hipSuccess;
-    size_t ring_bytes = 0;
+    RingFeed feed;
     J.n_obs = n_obs; J.n_pos = n_pos; J.record_bytes = p->rb;
     J.rec = s.h_in + s.off_rec; J.gbase = reinterpret_cast<uint32_t *>(s.h_in + s.off_gbase);
     J.pair_out = nullptr;
     J.cmin = s.cmin.data(); J.cmax = s.cmax.data(); J.cany = s.cany.data();
     J.cap_rec = p->cap_rec;
-    if (ring) {
-        // the copy-in queue starts here: every finished wave leaves for its place in the device arena while the next
-        // one is being written into the other half
-        HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-        const size_t half_bytes = (size_t)p->ring_half * p->rb, grp_bytes = (size_t)p->G * p->rb;
-        J.ring_groups = p->ring_half / p->G;
-        J.wave_begin = [&](int h) {
-            if (s.ring_busy[h]) { const hipError_t e = isx_wait_event(s.ev_ring[h]); if (e != hipSuccess && ring_err == hipSuccess) ring_err = e; s.ring_busy[h] = false; }
-        };
-        J.wave_flush = [&](int h, int64_t g0, int64_t g1) {
-            const size_t n = (size_t)(g1 - g0) * grp_bytes;
-            if (g0 == 0) ring_bytes = 0;                    // a layout that overflowed is written again from the start
-            hipError_t e = hipMemcpyAsync(d_rec + (size_t)g0 * grp_bytes, s.h_in + s.off_rec + (size_t)h * half_bytes, n, hipMemcpyHostToDevice, H2D(p, s));
-            if (e == hipSuccess) e = hipEventRecord(s.ev_ring[h], H2D(p, s));
-            if (e != hipSuccess && ring_err == hipSuccess) ring_err = e;
-            s.ring_busy[h] = true;
-            ring_bytes += n;
-        };
-    }
+    if ((rc = ring_feed_install(p, s, feed, J.ring_groups, J.wave_begin, J.wave_flush)) != ISX_OK) return rc;
     int erc = 0;
     for (int attempt = 0;; attempt++) {
         if (linkage) {
@@ -1117,7 +1334,7 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
             J.run_index_out = reinterpret_cast<uint32_t *>(s.h_in + s.off_ridx);
         }
         J.slack = p->slack;
-        ring_bytes = 0;
+        feed.bytes = 0;
         erc = isxenc::encode_obs(*p->pool, J);
         if (erc != isxenc::ENC_OK || !linkage || J.n_runs <= s.cap_runs || attempt == 1) break;
         // more pair-id runs than any batch of this slot had (short fragments): larger blocks, encode again
@@ -1129,7 +1346,7 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
         HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.d_runs), s.cap_runs * sizeof(uint2)));
     }
     const double t_enc = now_ms();
-    if (ring_err != hipSuccess) { isx_set_error(std::string("isx_pipe_submit: staging ring: ") + hipGetErrorString(ring_err)); return ISX_ERR_HIP; }
+    if (feed.err != hipSuccess) { isx_set_error(std::string("isx_pipe_submit: staging ring: ") + hipGetErrorString(feed.err)); return ISX_ERR_HIP; }
     if (erc == isxenc::ENC_CAPACITY) { isx_set_error("isx_pipe_submit: the stream jumps too often for the pipe's record capacity (raise jump_slack)"); return ISX_ERR_CAPACITY; }
     if (erc == isxenc::ENC_MM_RANGE) { isx_set_error("an observation has mm >= 256"); return ISX_ERR_MM_RANGE; }
     if (erc == isxenc::ENC_BAD_POS) { isx_set_error("observation gpos >= n_pos"); return ISX_ERR_ARG; }
@@ -1139,54 +1356,18 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
     }
     if (J.passes > 1 && J.n_groups_in > 0)            // remember how jumpy this stream is: the next batch gets its slack up front
         p->slack = std::max(p->slack, 1.25 * ((double)J.n_groups_real / (double)J.n_groups_in - 1.0) + 0.01);
-    s.ref_has_n = pack_ref2(*p->pool, ref, n_pos, s.h_in + s.off_ref, s.h_in + s.off_ref + ref2_bytes(n_pos));
+    s.ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, s.h_in + s.off_ref, s.h_in + s.off_ref + ref2_bytes(n_pos));
     memcpy(s.h_in + s.off_bounds, split_bounds, (size_t)(n_splits + 1) * sizeof(int64_t));
 
     // ---- this batch's geometry ----
     b->n_pos = n_pos; b->n_obs = n_obs; b->n_splits = n_splits; b->n_rec = (uint64_t)J.n_rec;
-    // without a count table to hand back, the position-sized tables travel shrunk (see finish_slot): clonality as the list of
-    // values other than 1.0, coverage in one byte for a shallow batch
-    b->sparse_out = dense && b->d_clon_list != nullptr;
-    b->cov8_out = b->sparse_out && (double)b->n_obs < 16.0 * (double)n_pos;
-    b->nib_out = b->cov8_out && b->lean && (double)b->n_obs < 6.0 * (double)n_pos;      // (mean depth below 6: most windows stay within 4 bits)
-    b->clon_dense = false;
-    b->rare_dense = !(b->lean && b->sparse_out) || (double)b->n_obs * 4.0 >= (double)p->prm.rarefied_coverage * (double)b->n_pos;
-    if (b->lev_sparse) b->lev_cov_bytes = (double)b->n_obs < 64.0 * (double)b->n_pos ? 1 : 2;      // (a level of a batch this shallow rarely reaches 255: the exact values of those that do travel in a list)
     b->n_pairs = (uint64_t)J.max_pair + 1;
-    const uint64_t n_chunks = b->n_rec / ISX_CHUNK;
-    b->packed = 0;
-    int W = batch_window_for(b, n_pos, false);
-    if (!dense) {
-        const int Wp = batch_window_for(b, n_pos, true);
-        if (!(p->prm.layout & ISX_LAYOUT_NO_PACKED_COUNTERS) &&
-            build_window_directory(s.cmin.data(), s.cmax.data(), s.cany.data(), n_chunks, Wp, n_pos, s.win) < 65536) { b->packed = 1; W = Wp; }
-    }
-    if (!b->packed) build_window_directory(s.cmin.data(), s.cmax.data(), s.cany.data(), n_chunks, W, n_pos, s.win);
-    b->W = W;
-    b->n_win = (int)s.win.size();
-    if (s.win.size() > (size_t)p->pp.max_pos / 64 + 2) { isx_set_error("internal: window directory larger than the arena"); return ISX_ERR_STATE; }
-    int rc = batch_set_geometry(b);
-    if (rc != ISX_OK) return rc;
-    if (!dense && !b->lev_sparse) {
-        const size_t used = (size_t)b->n_win * b->slab;
-        if (used > b->slab_region) { isx_set_error("internal: entry slabs larger than the slot's region"); return ISX_ERR_STATE; }
-        b->cap_ovf = b->cap_entries - used;
-    }
-    memcpy(s.h_in + s.off_win, s.win.data(), s.win.size() * sizeof(uint2));
-    b->d_bounds = reinterpret_cast<int64_t *>(s.d_in + s.off_bounds);
-    b->d_win = reinterpret_cast<uint2 *>(s.d_in + s.off_win);
-    b->d_ref = s.d_in + s.off_ref;
-    b->d_ref_n = s.ref_has_n ? s.d_in + s.off_ref + ref2_bytes(b->n_pos) : nullptr;
-    b->d_gbase = reinterpret_cast<uint32_t *>(s.d_in + s.off_gbase);
-    b->d_rec16 = p->rb == 2 ? reinterpret_cast<uint16_t *>(s.d_in + s.off_rec) : nullptr;
-    b->d_rec32 = p->rb == 4 ? reinterpret_cast<uint32_t *>(s.d_in + s.off_rec) : nullptr;
-    b->d_pair = nullptr;
-    b->d_pair_runs = linkage ? s.d_runs : nullptr;
-    b->d_run_index = linkage ? reinterpret_cast<uint32_t *>(s.d_in + s.off_ridx) : nullptr;
-    b->d_gpos16 = s.d_gpos16; b->gpos16_shift = 5;
+    if ((rc = slot_choose_windows(p, s, ISX_CHUNK, false)) != ISX_OK) return rc;
+    if ((rc = slot_shape_pass(p, s)) != ISX_OK) return rc;
+    slot_bind_inputs(p, s, nullptr);
     s.encode_ms = (float)(now_ms() - t0);
     s.encode_passes = J.passes;
-    if (getenv("ISX_PIPE_TIMING"))      // tuning aid (stderr only)
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe_submit] records %.2f ms (%d pass), reference + bounds + windows %.2f ms; %lld obs, %lld runs\n",
                 t_enc - t0, J.passes, now_ms() - t_enc, (long long)n_obs, (long long)J.n_runs);
 
@@ -1206,7 +1387,7 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
     if (ring) {             // the records left wave by wave; the tail is written on the device
         if (p->rb == 2) HIP_TRY(hipMemsetD8Async(reinterpret_cast<hipDeviceptr_t>(d_rec + (size_t)b->n_rec * 2), 0xFF, ISX_TAIL_BYTES, H2D(p, s)));
         else HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rec + (size_t)b->n_rec * 4), (int)ISX_PAD32, ISX_TAIL_BYTES / 4, H2D(p, s)));
-        if (ring_bytes != (size_t)b->n_rec * p->rb) { isx_set_error("internal: the staging ring did not carry the whole stream"); return ISX_ERR_STATE; }
+        if (feed.bytes != (size_t)b->n_rec * p->rb) { isx_set_error("internal: the staging ring did not carry the whole stream"); return ISX_ERR_STATE; }
     } else {
         if (p->rb == 2) memset(s.h_in + s.off_rec + (size_t)b->n_rec * 2, 0xFF, ISX_TAIL_BYTES);
         else std::fill_n(reinterpret_cast<uint32_t *>(s.h_in + s.off_rec + (size_t)b->n_rec * 4), ISX_TAIL_BYTES / 4, (uint32_t)ISX_PAD32);
@@ -1225,28 +1406,48 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
     return enqueue_pass(p, s, n_pos, ticket);
 }
 
+// The record pass of a read-level batch into the slot's staging: 64-byte segment records, or reference-delta records.  For those the
+// segments are compared with the reference here; pieces of segments with more than six differences take spare groups of their task's
+// region, and a batch that needs more than the pipe has learned so far is encoded a second time (ring mode: its waves simply travel
+// again).  Returns the encoder's status (isxenc::SEG_*).
+static int encode_reads(isx_pipe *p, Slot &s, isxenc::SegJob &J, bool planes_in, RingFeed &feed)
+{
+    s.encode_passes = 1;
+    if (!p->drec) return isxenc::encode_segs(*p->pool, J);
+    std::vector<int64_t> exact;
+    for (int attempt = 0;; attempt++) {
+        J.slack_groups = p->dslack;
+        J.task_groups = exact.empty() ? nullptr : exact.data();
+        feed.bytes = 0;
+        const int erc = planes_in ? isxenc::encode_planes(*p->pool, J) : isxenc::encode_delta(*p->pool, J);
+        if (erc != isxenc::SEG_CAPACITY || J.need_slack <= p->dslack || attempt != 0) return erc;
+        // the second attempt gives every task exactly what the first one found it needs; the pipe remembers the AVERAGE
+        // surplus (data that differs from the reference everywhere then fits at once; one task over a stretch where the
+        // reference is not A/C/T/G does not inflate the others)
+        exact = J.task_need;
+        int64_t tot = 0;
+        for (int64_t v : exact) tot += v;
+        const int64_t n_t = (int64_t)exact.size(), base_tot = J.n_rec / ISX_DREC_GROUP - n_t * p->dslack;
+        p->dslack = std::max<int64_t>(p->dslack, 1 + (tot - base_tot + n_t - 1) / std::max<int64_t>(n_t, 1));
+        s.encode_passes = 2;
+    }
+}
+
 // a read-level batch: `J` arrives with its input side set (isx_segs arrays, or a producer + the segment starts)
 // (bit-plane input -- J.in2 / J.produce_planes -- goes through encode_planes; its reference arrives as planes (`rp`) or as codes)
 static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t n_splits, const int64_t *split_bounds,
                               isxenc::SegJob &J, int64_t *ticket, const isx_ref_planes *rp)
 {
+    static const char who[] = "isx_pipe_submit_reads";
     const bool planes_in = J.in2.planes != nullptr || (bool)J.produce_planes || (J.n_seg == 0 && rp != nullptr);
-    if (n_pos > p->pp.max_pos || J.n_seg > p->pp.max_segs || n_splits > p->pp.max_splits) {
-        isx_set_error("isx_pipe_submit_reads: batch larger than the pipe was created for");
-        return ISX_ERR_CAPACITY;
-    }
-    if (split_bounds[0] != 0 || split_bounds[n_splits] != n_pos) { isx_set_error("split_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
-    for (int i = 0; i < n_splits; i++)
-        if (split_bounds[i + 1] <= split_bounds[i]) { isx_set_error("split_bounds must be strictly ascending"); return ISX_ERR_ARG; }
-    Slot &s = p->slots[(size_t)(p->next_ticket % (int64_t)p->slots.size())];
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (s.state != 0) { isx_set_error("isx_pipe_submit_reads: every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
-    }
-    isx_ctx *c = p->ctx;
+    int rc;
+    if ((rc = check_capacity(p, who, n_pos, J.n_seg, p->pp.max_segs, n_splits)) != ISX_OK) return rc;
+    if ((rc = check_split_bounds(n_pos, n_splits, split_bounds)) != ISX_OK) return rc;
+    Slot *slot = nullptr;
+    if ((rc = slot_acquire(p, who, &slot)) != ISX_OK) return rc;
+    Slot &s = *slot;
     isx_batch *b = s.b;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool dense = b->M == 1, linkage = p->prm.enable_linkage != 0;
+    const bool linkage = p->prm.enable_linkage != 0;
 
     // ---- host threads: records + group bases (+ pair ids) into pinned staging, reference codes, bounds ----
     const double t0 = now_ms();
@@ -1257,141 +1458,22 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
     J.cmin = s.cmin.data(); J.cmax = s.cmax.data(); J.cany = s.cany.data();
     J.cap_rec = p->cap_rec;
     const bool ring = p->ring_half > 0;
-    hipError_t ring_err = hipSuccess;
-    size_t ring_bytes = 0;
-    if (ring) {
-        // the copy-in queue starts here: every finished wave leaves for its place in the device arena while the next one is
-        // being written into the other half
-        HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-        const size_t half_bytes = (size_t)p->ring_half * (size_t)p->rb;
-        constexpr size_t grp_bytes = (size_t)ISX_SEG_GROUP * 64;           // (= ISX_DREC_GROUP * 32: a group is 1 KiB in both formats)
-        uint8_t *d_rec = s.d_in + s.off_rec;
-        J.ring_groups = p->ring_half / (int64_t)p->G;
-        J.wave_begin = [&s, &ring_err](int h) {
-            if (s.ring_busy[h]) { const hipError_t e = isx_wait_event(s.ev_ring[h]); if (e != hipSuccess && ring_err == hipSuccess) ring_err = e; s.ring_busy[h] = false; }
-        };
-        J.wave_flush = [&s, p, &ring_err, &ring_bytes, half_bytes, d_rec](int h, int64_t g0, int64_t g1) {
-            const size_t nb = (size_t)(g1 - g0) * grp_bytes;
-            hipError_t e = hipMemcpyAsync(d_rec + (size_t)g0 * grp_bytes, s.h_in + s.off_rec + (size_t)h * half_bytes, nb, hipMemcpyHostToDevice, H2D(p, s));
-            if (e == hipSuccess) e = hipEventRecord(s.ev_ring[h], H2D(p, s));
-            if (e != hipSuccess && ring_err == hipSuccess) ring_err = e;
-            s.ring_busy[h] = true;
-            ring_bytes += nb;
-        };
-    }
-    int erc;
-    double t_ref0 = 0.0;
-    bool early_ref = false, early_rec = false;
-    uint8_t *resident_ref = nullptr;            // the batch's reference planes already on the device (isx_ref_planes.key)
+    RingFeed feed;
+    if ((rc = ring_feed_install(p, s, feed, J.ring_groups, J.wave_begin, J.wave_flush)) != ISX_OK) return rc;
+    RefStage rs;
     if (planes_in) {
-        // the reference planes first, into staging: the record pass compares against that copy
+        // the reference planes first: the record pass compares against them
         if (!p->drec) { isx_set_error("bit-plane reads need a pipe whose batches travel as reference-delta records (one mm bin, or ISX_LAYOUT_MM_DELTA_RECORDS)"); return ISX_ERR_STATE; }
-        const double t_r = now_ms();
-        uint8_t *h2 = s.h_in + s.off_ref, *hn = h2 + ref2_bytes(n_pos);
-        if (rp && rp->key) {
-            auto it = p->ref_cache.find(rp->key);
-            if (it != p->ref_cache.end()) {
-                // the device already holds this reference: nothing is staged, nothing travels; the record pass compares against the
-                // caller's own planes
-                const isx_pipe::RefEntry &e = it->second;
-                if (e.n_pos != n_pos || e.has_n != (rp->nplane != nullptr && e.has_n) || e.sum != ref_plane_checksum(rp->plane2, n_pos)) {
-                    isx_set_error("isx_pipe_submit_planes: the reference key stands for other planes (positions / non-ACGT plane / content differ)");
-                    return ISX_ERR_ARG;
-                }
-                s.ref_has_n = e.has_n;
-                J.ref2 = rp->plane2; J.refn = e.has_n ? rp->nplane : nullptr;
-                resident_ref = e.d;
-                HIP_TRY(hipStreamWaitEvent(H2D(p, s), e.ready, 0));         // (the entry's own copy, enqueued by an earlier submit)
-                if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-                HIP_TRY(hipEventRecord(s.ev_h2da, H2D(p, s)));
-                early_ref = true;
-                t_ref0 = now_ms() - t_r;
-                goto ref_staged;
-            }
-        }
-        if (rp && !(rp->key && !p->ref_cache.count(rp->key) && p->ref_cache_budget.load(std::memory_order_relaxed) > 0) &&
-            isx_host_is_registered(rp->plane2, ((size_t)n_pos + 3) / 4) &&
-            (!rp->nplane || isx_host_is_registered(rp->nplane, ((size_t)n_pos + 7) / 8))) {
-            // the caller's planes are registered for the copy engine (isx_host_register): they leave from where they lie, nothing is
-            // staged, the record pass compares against them (a key's FIRST trip still goes through staging: its device copy is made of that)
-            bool any_n = false;
-            if (rp->nplane) any_n = plane_any(*p->pool, rp->nplane, ((size_t)n_pos + 7) / 8);
-            s.ref_has_n = any_n;
-            J.ref2 = rp->plane2; J.refn = any_n ? rp->nplane : nullptr;
-            t_ref0 = now_ms() - t_r;
-            if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-            HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, rp->plane2, ((size_t)n_pos + 3) / 4, hipMemcpyHostToDevice, H2D(p, s)));
-            if (any_n) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref + ref2_bytes(n_pos), rp->nplane, ((size_t)n_pos + 7) / 8, hipMemcpyHostToDevice, H2D(p, s)));
-            if (!ring) HIP_TRY(hipEventRecord(s.ev_h2da, H2D(p, s)));
-            early_ref = true;
-            goto ref_staged;
-        }
-        s.ref_has_n = rp ? copy_ref_planes(*p->pool, rp, n_pos, h2, hn) : pack_ref2(*p->pool, ref, n_pos, h2, hn);
-        J.ref2 = h2; J.refn = s.ref_has_n ? hn : nullptr;
-        t_ref0 = now_ms() - t_r;
-        // ... and leave at once: the DMA engine brings the reference in while the threads make the records
-        // (ISX_PIPE_LATE_DMA=1: every copy after the host pass, as before round 5 -- same-box A/B)
-        static const bool late_dma = getenv("ISX_PIPE_LATE_DMA") != nullptr;
-        if (late_dma) goto ref_staged;
-        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, h2, ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0), hipMemcpyHostToDevice, H2D(p, s)));
-        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2da, H2D(p, s)));
-        early_ref = true;
-        if (rp && rp->key && !resident_ref) {
-            // first trip of this key: a device-side copy of what just arrived stays with the pipe (while its budget lasts)
-            const size_t rb_all = ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0);
-            if (p->ref_cache_bytes + rb_all <= p->ref_cache_budget.load(std::memory_order_relaxed)) {
-                isx_pipe::RefEntry e;
-                bool ok = isx_dev_malloc(reinterpret_cast<void **>(&e.d), rb_all + 64) == hipSuccess && hipEventCreateWithFlags(&e.ready, hipEventDisableTiming) == hipSuccess;
-                ok = ok && hipMemcpyAsync(e.d, s.d_in + s.off_ref, rb_all, hipMemcpyDeviceToDevice, H2D(p, s)) == hipSuccess && hipEventRecord(e.ready, H2D(p, s)) == hipSuccess;
-                if (ok) {
-                    e.bytes = rb_all; e.n_pos = n_pos; e.has_n = s.ref_has_n; e.sum = ref_plane_checksum(rp->plane2, n_pos);
-                    p->ref_cache_bytes += rb_all;
-                    p->ref_cache.emplace(rp->key, e);
-                } else {                            // (no entry: the batch goes on with the planes that just travelled; nothing leaks)
-                    if (e.d) isx_dev_free(e.d);
-                    if (e.ready) (void)hipEventDestroy(e.ready);
-                    (void)hipGetLastError();
-                }
-            }
-        }
-    ref_staged:;
+        if ((rc = stage_reference(p, s, n_pos, ref, rp, J, &rs)) != ISX_OK) return rc;
     }
-    if (p->drec) {
-        // reference-delta records: the segments are compared with the reference here; pieces of segments with more than six
-        // differences take spare groups of their task's region -- a batch that needs more than the pipe has learned so far is
-        // encoded a second time (ring mode: its waves simply travel again)
-        J.ref = ref;
-        std::vector<int64_t> exact;
-        s.encode_passes = 1;
-        for (int attempt = 0;; attempt++) {
-            J.slack_groups = p->dslack;
-            J.task_groups = exact.empty() ? nullptr : exact.data();
-            ring_bytes = 0;
-            erc = planes_in ? isxenc::encode_planes(*p->pool, J) : isxenc::encode_delta(*p->pool, J);
-            if (erc == isxenc::SEG_CAPACITY && J.need_slack > p->dslack && attempt == 0) {
-                // the second attempt gives every task exactly what the first one found it needs; the pipe remembers the AVERAGE
-                // surplus (data that differs from the reference everywhere then fits at once; one task over a stretch where the
-                // reference is not A/C/T/G does not inflate the others)
-                exact = J.task_need;
-                int64_t tot = 0;
-                for (int64_t v : exact) tot += v;
-                const int64_t n_t = (int64_t)exact.size(), base_tot = J.n_rec / ISX_DREC_GROUP - n_t * p->dslack;
-                p->dslack = std::max<int64_t>(p->dslack, 1 + (tot - base_tot + n_t - 1) / std::max<int64_t>(n_t, 1));
-                s.encode_passes = 2;
-                continue;
-            }
-            break;
-        }
-    } else erc = isxenc::encode_segs(*p->pool, J);
+    if (p->drec) J.ref = ref;
+    const int erc = encode_reads(p, s, J, planes_in, feed);
     const double t_enc = now_ms();
-    if (ring_err != hipSuccess) { isx_set_error(std::string("isx_pipe_submit_reads: staging ring: ") + hipGetErrorString(ring_err)); return ISX_ERR_HIP; }
-    if (erc == isxenc::SEG_CAPACITY) { isx_set_error("isx_pipe_submit_reads: the stream jumps too often for the pipe's record capacity (raise jump_slack)"); return ISX_ERR_CAPACITY; }
-    if (erc == isxenc::SEG_MM_RANGE) { isx_set_error("a segment has mm >= n_mm_bins"); return ISX_ERR_MM_RANGE; }
-    if (erc == isxenc::SEG_BAD_POS) { isx_set_error("a segment reaches beyond n_pos"); return ISX_ERR_ARG; }
-    if (erc == isxenc::SEG_BAD_LEN) { isx_set_error("a segment's length is not in [1, 150]"); return ISX_ERR_ARG; }
+    if (feed.err != hipSuccess) { isx_set_error(std::string("isx_pipe_submit_reads: staging ring: ") + hipGetErrorString(feed.err)); return ISX_ERR_HIP; }
+    if ((rc = seg_status_error(erc, "isx_pipe_submit_reads: the stream jumps too often for the pipe's record capacity (raise jump_slack)", ISX_ERR_CAPACITY)) != ISX_OK) return rc;
     if (J.n_bases > p->pp.max_obs) { isx_set_error("isx_pipe_submit_reads: more bases than the pipe's max_obs"); return ISX_ERR_CAPACITY; }
-    if (early_ref && !ring) {
+    bool early_rec = false;
+    if (rs.early && !ring) {
         // the records leave as soon as they exist; the window directory below is made while they travel
         const size_t gb_bytes0 = (size_t)(J.n_rec / (int64_t)p->G) * sizeof(uint32_t), rec_bytes0 = (size_t)J.n_rec * (size_t)p->rb;
         HIP_TRY(hipEventRecord(s.ev_h2db, H2D(p, s)));
@@ -1405,60 +1487,24 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
         }
         early_rec = true;
     }
-    if (!planes_in) s.ref_has_n = pack_ref2(*p->pool, ref, n_pos, s.h_in + s.off_ref, s.h_in + s.off_ref + ref2_bytes(n_pos));
+    if (!planes_in) s.ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, s.h_in + s.off_ref, s.h_in + s.off_ref + ref2_bytes(n_pos));
     const double t_ref = now_ms();
     memcpy(s.h_in + s.off_bounds, split_bounds, (size_t)(n_splits + 1) * sizeof(int64_t));
 
     // ---- this batch's geometry ----
     b->n_pos = n_pos; b->n_obs = J.n_bases; b->n_splits = n_splits; b->n_rec = (uint64_t)J.n_rec;
-    // without a count table to hand back, the position-sized tables travel shrunk (see finish_slot): clonality as the list of
-    // values other than 1.0, coverage in one byte for a shallow batch
-    b->sparse_out = dense && b->d_clon_list != nullptr;
-    b->cov8_out = b->sparse_out && (double)b->n_obs < 16.0 * (double)n_pos;
-    b->nib_out = b->cov8_out && b->lean && (double)b->n_obs < 6.0 * (double)n_pos;      // (mean depth below 6: most windows stay within 4 bits)
-    b->clon_dense = false;
-    b->rare_dense = !(b->lean && b->sparse_out) || (double)b->n_obs * 4.0 >= (double)p->prm.rarefied_coverage * (double)b->n_pos;
-    if (b->lev_sparse) b->lev_cov_bytes = (double)b->n_obs < 64.0 * (double)b->n_pos ? 1 : 2;      // (a level of a batch this shallow rarely reaches 255: the exact values of those that do travel in a list)
     b->n_pairs = (uint64_t)J.max_pair + 1;
-    const uint64_t n_chunks = b->n_rec / p->G;
-    b->packed = 0;
-    int W = batch_window_for(b, n_pos, false);
-    if (!dense || p->drec) {
-        const int Wp = batch_window_for(b, n_pos, true);
-        if (!(p->prm.layout & ISX_LAYOUT_NO_PACKED_COUNTERS) &&
-            build_window_directory_mt(*p->pool, s.cmin.data(), s.cmax.data(), s.cany.data(), n_chunks, Wp, n_pos, s.win, p->G, s.dir_pmax, s.dir_smin) < (p->drec ? 32768u : 65536u)) { b->packed = 1; W = Wp; }
-    }
-    if (!b->packed) build_window_directory_mt(*p->pool, s.cmin.data(), s.cmax.data(), s.cany.data(), n_chunks, W, n_pos, s.win, p->G, s.dir_pmax, s.dir_smin);
-    b->W = W;
-    b->n_win = (int)s.win.size();
-    if (s.win.size() > (size_t)p->pp.max_pos / 64 + 2) { isx_set_error("internal: window directory larger than the arena"); return ISX_ERR_STATE; }
-    int rc = batch_set_geometry(b);
-    if (rc != ISX_OK) return rc;
-    if (!dense && !b->lev_sparse) {
-        const size_t used = (size_t)b->n_win * b->slab;
-        if (used > b->slab_region) { isx_set_error("internal: entry slabs larger than the slot's region"); return ISX_ERR_STATE; }
-        b->cap_ovf = b->cap_entries - used;
-    }
-    memcpy(s.h_in + s.off_win, s.win.data(), s.win.size() * sizeof(uint2));
-    b->d_bounds = reinterpret_cast<int64_t *>(s.d_in + s.off_bounds);
-    b->d_win = reinterpret_cast<uint2 *>(s.d_in + s.off_win);
-    b->d_ref = resident_ref ? resident_ref : s.d_in + s.off_ref;
-    b->d_ref_n = s.ref_has_n ? b->d_ref + ref2_bytes(b->n_pos) : nullptr;
-    b->d_gbase = reinterpret_cast<uint32_t *>(s.d_in + s.off_gbase);
-    b->d_seg = p->drec ? nullptr : reinterpret_cast<uint4 *>(s.d_in + s.off_rec);
-    b->d_drec = p->drec ? reinterpret_cast<uint4 *>(s.d_in + s.off_rec) : nullptr;
-    b->d_rec16 = nullptr; b->d_rec32 = nullptr;
-    b->d_pair = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.d_in + s.off_pairs) : nullptr;
-    b->d_pair_runs = nullptr; b->d_run_index = nullptr; b->n_runs = 0;
+    if ((rc = slot_choose_windows(p, s, p->G, true)) != ISX_OK) return rc;
+    if ((rc = slot_shape_pass(p, s)) != ISX_OK) return rc;
+    slot_bind_inputs(p, s, rs.resident);
     s.encode_ms = (float)(now_ms() - t0);
-    if (!p->drec) s.encode_passes = 1;
-    if (getenv("ISX_PIPE_TIMING"))      // tuning aid (stderr only)
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe_submit_reads] records %.2f ms, reference %.2f ms, bounds + windows %.2f ms; %lld segments, %lld records%s\n",
-                t_enc - t0 - t_ref0, t_ref - t_enc + t_ref0, now_ms() - t_ref, (long long)J.n_seg, (long long)J.n_rec, planes_in ? " (bit planes)" : "");
+                t_enc - t0 - rs.host_ms, t_ref - t_enc + rs.host_ms, now_ms() - t_ref, (long long)J.n_seg, (long long)J.n_rec, planes_in ? " (bit planes)" : "");
     const double t_q0 = now_ms();
 
     // ---- copy-in queue: bounds | windows | reference codes, then group bases (| pair ids) | records ----
-    if (!ring && !early_ref) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
+    if (!ring && !rs.early) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
     const size_t ref_bytes = ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0);   // 2-bit plane (+ the non-ACGT bit plane)
     const size_t head = (size_t)(n_splits + 1) * sizeof(int64_t) + s.win.size() * sizeof(uint2) + ref_bytes;
     const size_t gb_bytes = (size_t)(b->n_rec / p->G) * sizeof(uint32_t), rec_bytes = (size_t)b->n_rec * (size_t)p->rb;
@@ -1469,11 +1515,11 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
         HIP_TRY(hipMemcpyAsync(s.d_in + s.off_bounds, s.h_in + s.off_bounds, (size_t)(n_splits + 1) * sizeof(int64_t), hipMemcpyHostToDevice, H2D(p, s)));
         HIP_TRY(hipMemcpyAsync(s.d_in + s.off_win, s.h_in + s.off_win, s.win.size() * sizeof(uint2), hipMemcpyHostToDevice, H2D(p, s)));
     }
-    if (!early_ref) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, s.h_in + s.off_ref, ref_bytes, hipMemcpyHostToDevice, H2D(p, s)));
+    if (!rs.early) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, s.h_in + s.off_ref, ref_bytes, hipMemcpyHostToDevice, H2D(p, s)));
     if (!early_rec) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_gbase, s.h_in + s.off_gbase, gb_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    if (ring) { if (ring_bytes != rec_bytes) { isx_set_error("internal: the staging ring did not carry the whole stream"); return ISX_ERR_STATE; } }
+    if (ring) { if (feed.bytes != rec_bytes) { isx_set_error("internal: the staging ring did not carry the whole stream"); return ISX_ERR_STATE; } }
     else if (!early_rec) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_rec, s.h_in + s.off_rec, rec_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    s.h2d_bytes = (int64_t)(head + gb_bytes + rec_bytes) - (resident_ref ? (int64_t)ref_bytes : 0);
+    s.h2d_bytes = (int64_t)(head + gb_bytes + rec_bytes) - (rs.resident ? (int64_t)ref_bytes : 0);
     if (linkage && !p->drec) {
         HIP_TRY(hipMemcpyAsync(s.d_in + s.off_pairs, s.h_in + s.off_pairs, (size_t)b->n_rec * sizeof(uint32_t), hipMemcpyHostToDevice, H2D(p, s)));
         s.h2d_bytes += (int64_t)b->n_rec * 4;
@@ -1482,7 +1528,7 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
     s.h2d_split = early_rec;
     const double t_q1 = now_ms();
     rc = enqueue_pass(p, s, n_pos, ticket);
-    if (getenv("ISX_PIPE_TIMING")) fprintf(stderr, "[isx_pipe_submit_reads] copy-in queue %.2f ms, pass + copy-out queue %.2f ms\n", t_q1 - t_q0, now_ms() - t_q1);
+    if (pipe_timing) fprintf(stderr, "[isx_pipe_submit_reads] copy-in queue %.2f ms, pass + copy-out queue %.2f ms\n", t_q1 - t_q0, now_ms() - t_q1);
     return rc;
 }
 
@@ -1514,13 +1560,9 @@ static int stage_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, const is
     if (!p->segs) { isx_set_error("isx_pipe_stage_reads: not a read-level pipe (isx_pipe_params.max_segs == 0)"); return ISX_ERR_STATE; }
     const bool linkage = p->prm.enable_linkage != 0;
     if (linkage && segs->n_seg && !segs->pair) { isx_set_error("linkage needs the pair array"); return ISX_ERR_ARG; }
-    if (n_pos > p->pp.max_pos || segs->n_seg > p->pp.max_segs || n_splits > p->pp.max_splits) {
-        isx_set_error("isx_pipe_stage_reads: batch larger than the pipe was created for");
-        return ISX_ERR_CAPACITY;
-    }
-    if (split_bounds[0] != 0 || split_bounds[n_splits] != n_pos) { isx_set_error("split_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
-    for (int i = 0; i < n_splits; i++)
-        if (split_bounds[i + 1] <= split_bounds[i]) { isx_set_error("split_bounds must be strictly ascending"); return ISX_ERR_ARG; }
+    int rc;
+    if ((rc = check_capacity(p, "isx_pipe_stage_reads", n_pos, segs->n_seg, p->pp.max_segs, n_splits)) != ISX_OK) return rc;
+    if ((rc = check_split_bounds(n_pos, n_splits, split_bounds)) != ISX_OK) return rc;
     HIP_TRY(hipSetDevice(p->ctx->device));
     const double t0 = now_ms();
     std::unique_ptr<isx_wire, void (*)(isx_wire *)> w(new isx_wire(), isx_wire_free);
@@ -1566,7 +1608,7 @@ static int stage_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, const is
         int erc;
         if (reads) {                     // the reference planes first (the record pass compares against the image's copy)
             uint8_t *h2 = w->h + w->o_ref, *hn = h2 + ref2_bytes(n_pos);
-            w->ref_has_n = rp ? copy_ref_planes(*p->pool, rp, n_pos, h2, hn) : pack_ref2(*p->pool, ref, n_pos, h2, hn);
+            w->ref_has_n = rp ? copy_ref_planes(*p->pool, rp, n_pos, h2, hn) : isxenc::pack_ref_planes(*p->pool, ref, n_pos, h2, hn);
             J.ref2 = h2; J.refn = w->ref_has_n ? hn : nullptr;
         }
         if (p->drec) {
@@ -1575,10 +1617,7 @@ static int stage_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, const is
             erc = reads ? isxenc::encode_planes(*p->pool, J) : isxenc::encode_delta(*p->pool, J);
             if (erc == isxenc::SEG_CAPACITY && J.need_slack > p->dslack && attempt == 0) { exact = J.task_need; w->encode_passes = 2; continue; }
         } else erc = isxenc::encode_segs(*p->pool, J);
-        if (erc == isxenc::SEG_CAPACITY) { isx_set_error("isx_pipe_stage_reads: the stream does not fit the record capacity"); return ISX_ERR_CAPACITY; }
-        if (erc == isxenc::SEG_MM_RANGE) { isx_set_error("a segment has mm >= n_mm_bins"); return ISX_ERR_MM_RANGE; }
-        if (erc == isxenc::SEG_BAD_POS) { isx_set_error("a segment reaches beyond n_pos"); return ISX_ERR_ARG; }
-        if (erc == isxenc::SEG_BAD_LEN) { isx_set_error("a segment's length is not in [1, 150]"); return ISX_ERR_ARG; }
+        if ((rc = seg_status_error(erc, "isx_pipe_stage_reads: the stream does not fit the record capacity", ISX_ERR_CAPACITY)) != ISX_OK) return rc;
         break;
     }
     if (J.n_bases > p->pp.max_obs) { isx_set_error("isx_pipe_stage_reads: more bases than the pipe's max_obs"); return ISX_ERR_CAPACITY; }
@@ -1586,22 +1625,14 @@ static int stage_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, const is
     w->gbase_bytes = (size_t)(J.n_rec / (int64_t)G) * sizeof(uint32_t);
     w->rec_bytes = (size_t)J.n_rec * rb;
     w->pairs_bytes = linkage && !p->drec ? (size_t)J.n_rec * sizeof(uint32_t) : 0;
-    if (!reads) w->ref_has_n = pack_ref2(*p->pool, ref, n_pos, w->h + w->o_ref, w->h + w->o_ref + ref2_bytes(n_pos));
+    if (!reads) w->ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, w->h + w->o_ref, w->h + w->o_ref + ref2_bytes(n_pos));
     if (!w->ref_has_n) w->ref_bytes = ref2_bytes(n_pos);
     memcpy(w->h + w->o_bounds, split_bounds, w->bounds_bytes);
     {   // the window directory, for the window this pipe's kernels will use on a batch of n_pos positions
-        const uint64_t n_chunks = (uint64_t)J.n_rec / G;
         std::vector<uint2> win;
         std::vector<uint32_t> dir_pmax, dir_smin;
-        w->packed = 0;
-        int W = batch_window_for(b0, n_pos, false);
-        if (M > 1 || p->drec) {
-            const int Wp = batch_window_for(b0, n_pos, true);
-            if (!(p->prm.layout & ISX_LAYOUT_NO_PACKED_COUNTERS) &&
-                build_window_directory_mt(*p->pool, cmin.data(), cmax.data(), cany.data(), n_chunks, Wp, n_pos, win, (uint32_t)G, dir_pmax, dir_smin) < (p->drec ? 32768u : 65536u)) { w->packed = 1; W = Wp; }
-        }
-        if (!w->packed) build_window_directory_mt(*p->pool, cmin.data(), cmax.data(), cany.data(), n_chunks, W, n_pos, win, (uint32_t)G, dir_pmax, dir_smin);
-        w->W = W;
+        DirThreads mt{*p->pool, dir_pmax, dir_smin};
+        w->W = choose_windows(b0, n_pos, ChunkDir{cmin.data(), cmax.data(), cany.data(), (uint64_t)J.n_rec / G, (uint32_t)G}, &mt, win, &w->packed);
         w->win_bytes = win.size() * sizeof(uint2);
         if (w->win_bytes > ((size_t)n_pos / 64 + 2) * sizeof(uint2) || win.size() > (size_t)p->pp.max_pos / 64 + 2) { isx_set_error("internal: window directory larger than its region"); return ISX_ERR_STATE; }
         memcpy(w->h + w->o_win, win.data(), w->win_bytes);
@@ -1667,45 +1698,19 @@ int isx_pipe_submit_wire(isx_pipe *p, const isx_wire *w, int64_t *ticket)
     if (!p || !w || !ticket) { isx_set_error("isx_pipe_submit_wire: bad argument"); return ISX_ERR_ARG; }
     if (w->pipe != p) { isx_set_error("isx_pipe_submit_wire: the batch was staged for another pipe"); return ISX_ERR_ARG; }
     drain_stager(p);
-    Slot &s = p->slots[(size_t)(p->next_ticket % (int64_t)p->slots.size())];
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (s.state != 0) { isx_set_error("isx_pipe_submit_wire: every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
-    }
-    isx_ctx *c = p->ctx;
-    isx_batch *b = s.b;
-    HIP_TRY(hipSetDevice(c->device));
-    const double t0 = now_ms();
-    const bool dense = b->M == 1, linkage = p->prm.enable_linkage != 0;
-    b->n_pos = w->n_pos; b->n_obs = w->n_bases; b->n_splits = w->n_splits; b->n_rec = (uint64_t)w->n_rec;
-    s.ref_has_n = w->ref_has_n;
-    b->sparse_out = dense && b->d_clon_list != nullptr;
-    b->cov8_out = b->sparse_out && (double)b->n_obs < 16.0 * (double)w->n_pos;
-    b->nib_out = b->cov8_out && b->lean && (double)b->n_obs < 6.0 * (double)w->n_pos;
-    b->clon_dense = false;
-    b->rare_dense = !(b->lean && b->sparse_out) || (double)b->n_obs * 4.0 >= (double)p->prm.rarefied_coverage * (double)b->n_pos;
-    if (b->lev_sparse) b->lev_cov_bytes = (double)b->n_obs < 64.0 * (double)b->n_pos ? 1 : 2;      // (a level of a batch this shallow rarely reaches 255: the exact values of those that do travel in a list)
-    b->n_pairs = w->n_pairs;
-    b->packed = w->packed; b->W = w->W;
-    b->n_win = (int)(w->win_bytes / sizeof(uint2));
-    int rc = batch_set_geometry(b);
+    Slot *slot = nullptr;
+    int rc = slot_acquire(p, "isx_pipe_submit_wire", &slot);
     if (rc != ISX_OK) return rc;
-    if (!dense && !b->lev_sparse) {
-        const size_t used = (size_t)b->n_win * b->slab;
-        if (used > b->slab_region) { isx_set_error("internal: entry slabs larger than the slot's region"); return ISX_ERR_STATE; }
-        b->cap_ovf = b->cap_entries - used;
-    }
-    b->d_bounds = reinterpret_cast<int64_t *>(s.d_in + s.off_bounds);
-    b->d_win = reinterpret_cast<uint2 *>(s.d_in + s.off_win);
-    uint8_t *const dref = w->d_ref ? w->d_ref : s.d_in + s.off_ref;         // (a kept reference: the wire's own device copy, nothing to bring in)
-    b->d_ref = dref;
-    b->d_ref_n = s.ref_has_n ? dref + ref2_bytes(b->n_pos) : nullptr;
-    b->d_gbase = reinterpret_cast<uint32_t *>(s.d_in + s.off_gbase);
-    b->d_seg = p->drec ? nullptr : reinterpret_cast<uint4 *>(s.d_in + s.off_rec);
-    b->d_drec = p->drec ? reinterpret_cast<uint4 *>(s.d_in + s.off_rec) : nullptr;
-    b->d_rec16 = nullptr; b->d_rec32 = nullptr;
-    b->d_pair = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.d_in + s.off_pairs) : nullptr;
-    b->d_pair_runs = nullptr; b->d_run_index = nullptr; b->n_runs = 0;
+    Slot &s = *slot;
+    isx_batch *b = s.b;
+    const double t0 = now_ms();
+    b->n_pos = w->n_pos; b->n_obs = w->n_bases; b->n_splits = w->n_splits; b->n_rec = (uint64_t)w->n_rec;
+    b->n_pairs = w->n_pairs;
+    s.ref_has_n = w->ref_has_n;
+    b->packed = w->packed; b->W = w->W;             // the choice stage_common made, replayed
+    b->n_win = (int)(w->win_bytes / sizeof(uint2));
+    if ((rc = slot_shape_pass(p, s)) != ISX_OK) return rc;
+    slot_bind_inputs(p, s, w->d_ref);               // (a kept reference: the wire's own device copy, nothing to bring in)
     HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
     HIP_TRY(hipMemcpyAsync(s.d_in + s.off_bounds, w->h + w->o_bounds, w->bounds_bytes, hipMemcpyHostToDevice, H2D(p, s)));
     HIP_TRY(hipMemcpyAsync(s.d_in + s.off_win, w->h + w->o_win, w->win_bytes, hipMemcpyHostToDevice, H2D(p, s)));
@@ -1732,29 +1737,11 @@ int isx_pipe_submit_reads(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_
     if (!p->segs) { isx_set_error("isx_pipe_submit_reads: not a read-level pipe (isx_pipe_params.max_segs == 0)"); return ISX_ERR_STATE; }
     if (p->prm.enable_linkage && segs->n_seg && !segs->pair) { isx_set_error("linkage needs the pair array"); return ISX_ERR_ARG; }
     if (p->stager.joinable()) {
-        // queued for the stager: only what can be said without touching the segments is checked here, the rest comes back
-        // through isx_pipe_collect.  The caller's arrays stay its own and unchanged until that call (or isx_pipe_release).
-        if (n_pos > p->pp.max_pos || segs->n_seg > p->pp.max_segs || n_splits > p->pp.max_splits) {
-            isx_set_error("isx_pipe_submit_reads: batch larger than the pipe was created for");
-            return ISX_ERR_CAPACITY;
-        }
         isx_pipe::StageJob job;
         job.n_pos = n_pos; job.ref = ref; job.segs = *segs;
         if (!p->prm.enable_linkage) job.segs.pair = nullptr;
         job.bounds.assign(split_bounds, split_bounds + n_splits + 1);
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            const int64_t t = p->next_promise, n = (int64_t)p->slots.size();
-            const Slot &s = p->slots[(size_t)(t % n)];
-            // the slot is free when the batch that had it last (ticket t - n) was staged, finished and released
-            if (t - n >= p->next_ticket || s.state != 0) { isx_set_error("isx_pipe_submit_reads: every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
-            job.ticket = t;
-            p->next_promise = t + 1;
-            *ticket = t;
-            p->stage_q.push_back(std::move(job));
-        }
-        p->cv_stage.notify_one();
-        return ISX_OK;
+        return queue_for_stager(p, std::move(job), "isx_pipe_submit_reads", ticket);
     }
     isxenc::SegJob J;
     J.in = *segs; J.n_seg = segs->n_seg;
@@ -1772,27 +1759,12 @@ int isx_pipe_submit_planes(isx_pipe *p, int64_t n_pos, const isx_ref_planes *ref
     }
     if (!p->segs || !p->drec) { isx_set_error("isx_pipe_submit_planes: bit-plane reads need a read-level pipe (max_segs > 0) with one mm bin (n_mm_bins == 1) or ISX_LAYOUT_MM_DELTA_RECORDS"); return ISX_ERR_STATE; }
     if (p->prm.enable_linkage && reads->n_seg && !reads->pair) { isx_set_error("linkage needs the pair array"); return ISX_ERR_ARG; }
-    if (p->stager.joinable()) {         // queued for the stager (see isx_pipe_submit_reads): the caller's arrays stay valid and unchanged until collect / release
-        if (n_pos > p->pp.max_pos || reads->n_seg > p->pp.max_segs || n_splits > p->pp.max_splits) {
-            isx_set_error("isx_pipe_submit_planes: batch larger than the pipe was created for");
-            return ISX_ERR_CAPACITY;
-        }
+    if (p->stager.joinable()) {
         isx_pipe::StageJob job;
         job.n_pos = n_pos; job.ref = nullptr; job.planes = true; job.reads = *reads; job.rp = *ref;
         if (!p->prm.enable_linkage) job.reads.pair = nullptr;
         job.bounds.assign(split_bounds, split_bounds + n_splits + 1);
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            const int64_t t = p->next_promise, n = (int64_t)p->slots.size();
-            const Slot &s = p->slots[(size_t)(t % n)];
-            if (t - n >= p->next_ticket || s.state != 0) { isx_set_error("isx_pipe_submit_planes: every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
-            job.ticket = t;
-            p->next_promise = t + 1;
-            *ticket = t;
-            p->stage_q.push_back(std::move(job));
-        }
-        p->cv_stage.notify_one();
-        return ISX_OK;
+        return queue_for_stager(p, std::move(job), "isx_pipe_submit_planes", ticket);
     }
     isxenc::SegJob J;
     J.in2 = *reads; J.n_seg = reads->n_seg;
@@ -1871,7 +1843,7 @@ int isx_pipe_submit_bam(isx_pipe *p, isx_bam *bam, const struct isx_bam_params_s
         if (s.ticket == *ticket && s.state == 1) s.dead_batch = Q.release();
     }
     if (Q) bam_batch_retire(Q.release());
-    if (getenv("ISX_PIPE_TIMING"))      // tuning aid (stderr only)
+    if (pipe_timing)
         fprintf(stderr, "[isx_pipe_submit_bam] prepare %.1f ms, encode + enqueue %.1f ms, free %.1f ms\n", t_prep - t_in, t_sub - t_prep, now_ms() - t_sub);
     return rc;
 }
