@@ -101,7 +101,10 @@ typedef struct {
                                          * 24..30 of a segment's header (k_pileup_mm materialises every level's coverage-difference row) instead of
                                          * the 64-byte segment records.  Half the bytes over PCIe; measured (round 6) the kernel is
                                          * no faster -- the per-level prefix sums and the wider LDS rows eat what the shorter stream saves -- and
-                                         * the host stager of isx_segs input costs twice the segment records': opt-in, not the default */
+                                         * the host stager of isx_segs input costs twice the segment records'.  At this interface the bit is opt-in
+                                         * (0 = segment records).  profile_bam sets it whenever mm profiling is on (n_mm_bins > 1), with jump_slack
+                                         * 1.0: its front end hands bit planes over, whose stager is the cheap one.  The level-sparse hand-back
+                                         * (isx_pipe_result.lev_*) covers n_mm_bins <= 32; with 33..128 bins a pipe hands 32-byte entries back */
 
 #define ISX_LAYOUT_NO_STRIPES 64         /* one-mm-bin reference-delta batches without a count table (pipe slots): the round-4 epilogue -- every position
                                          * gets the reference base's count and walks the first epilogue pass -- instead of the stripe path (a thread owns

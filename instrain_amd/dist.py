@@ -209,9 +209,7 @@ def profile_bam_sharded(bam, s2s, null_model, rank, world, gather=True, device=N
     from . import engine
     from ._lib import LD_DT, SCAFFOLD_LEVEL_DT, SNV_DT
     from .profile import profile_utilities as pu
-    fkw = dict(min_read_ani=kwargs.get('min_read_ani', 0.95), min_mapq=kwargs.get('min_mapq', -1),
-               max_insert_relative=kwargs.get('max_insert_relative', 3), min_insert=kwargs.get('min_insert', 50),
-               pairing_filter=kwargs.get('pairing_filter', 'paired_only'))
+    fkw = pu.read_filter_flags(kwargs)
     sharded_scan = world > 1 and kwargs.get('scan', 'sharded') == 'sharded'
     bf = engine.BamFile(bam, threads=int(kwargs.get('host_threads', 0)))
     try:

@@ -11,10 +11,12 @@ profile_bam keeps the reference's contract (profile/__init__.py:7-18):
   * a scaffold that cannot be profiled (not in the BAM, no / wrong sequence, a failing batch) is logged with the
     reference's "SplitException" line and dropped -- the others go on (profile_utilities.py:100-111, 154-156).
 """
+import functools
 import logging
 import os
 import time
 import traceback
+import types
 
 import numpy as np
 import pandas as pd
@@ -604,14 +606,9 @@ def profile_splits(ctx, scaffolds, sequences, obs, pair, null_model, n_mm_bins, 
     min_snp = int(kwargs.get('min_snp', 10))
     lut, fb = null_model_lut(null_model)
     ctx.set_null_model(lut, fb)
-    bounds, s_scaff, s_num, s_off, s_len = [], [], [], [], []
-    off = 0
-    for name, seq in zip(scaffolds, sequences):
-        for i, (s, e) in enumerate(iterate_splits(len(seq), window_length)):
-            bounds.append(off + s)
-            s_scaff.append(name); s_num.append(i); s_off.append(off); s_len.append(e - s + 1)
-        off += len(seq)
-    bounds.append(off)
+    bounds, s_scaff, s_num, s_off, s_len, _ = split_table(
+        (name, len(seq), [(i, s, e) for i, (s, e) in enumerate(iterate_splits(len(seq), window_length))])
+        for name, seq in zip(scaffolds, sequences))
     ref = np.concatenate([engine.encode_seq(s) for s in sequences])
     b = engine.Batch(ctx, ref, bounds, obs, pair, min_cov=min_cov, min_freq=min_freq, min_snp=min_snp,
                      rarefied_coverage=int(kwargs.get('rarefied_coverage', 5)), n_mm_bins=n_mm_bins,
@@ -642,6 +639,18 @@ def profile_splits(ctx, scaffolds, sequences, obs, pair, null_model, n_mm_bins, 
 def _failure_log(scaffold, split_number):
     t = time.strftime('%m-%d %H:%M')
     return "\n{1} DEBUG FAILURE SplitException {0} {2}\n".format(scaffold, t, split_number)   # profile_utilities.py:108-110
+
+
+def _fail(logs, scaffold, split_numbers, exc=None):
+    """a scaffold that is dropped: its exception on stdout, the reference's line for every one of its splits"""
+    if exc is not None:
+        print(exc)
+        traceback.print_exc()
+    for n in split_numbers:
+        line = _failure_log(scaffold, n)
+        logging.error(line)
+        if logs is not None:
+            logs.append(line)
 
 
 def plan_scaffolds(fasta_db, wanted_lengths, window_length):
@@ -679,9 +688,390 @@ def plan_scaffolds(fasta_db, wanted_lengths, window_length):
     return plan, bad
 
 
+def split_table(scaffolds):
+    """(name, length, [(split_number, start, end), ...]) of scaffolds laid end to end -> the flat split table of their batch: bounds (every
+    split's first flat position + the total length), per split its scaffold / number / scaffold offset / length, and first_split (every
+    scaffold's first row + the row count)"""
+    bounds, s_scaff, s_num, s_off, s_len, first_split = [], [], [], [], [], []
+    off = 0
+    for name, length, splits in scaffolds:
+        first_split.append(len(bounds))
+        for num, s, e in splits:
+            bounds.append(off + s)
+            s_scaff.append(name); s_num.append(num); s_off.append(off); s_len.append(e - s + 1)
+        off += length
+    first_split.append(len(bounds))
+    bounds.append(off)
+    return bounds, s_scaff, s_num, s_off, s_len, first_split
+
+
+def read_filter_flags(kwargs):
+    """the read filter's flags with the CLI's defaults (filter_reads.py): what BamFile.filter and the expansion take"""
+    return dict(min_read_ani=kwargs.get('min_read_ani', 0.95), min_mapq=kwargs.get('min_mapq', -1),
+                max_insert_relative=kwargs.get('max_insert_relative', 3), min_insert=kwargs.get('min_insert', 50),
+                pairing_filter=kwargs.get('pairing_filter', 'paired_only'))
+
+
+def profile_options(kwargs):
+    """profile_bam's kwargs parsed once: every default of the run is here and nowhere else.  pipe_depth / layout / jump_slack stay None
+    unless the caller names them: their defaults follow from the run (number of batches, mm levels; pipe_depth_of, open_pipe)."""
+    o = types.SimpleNamespace()
+    o.window_length = int(kwargs.get('window_length', 10000))
+    o.skip_mm = bool(kwargs.get('skip_mm_profiling', False))
+    o.min_cov = int(kwargs.get('min_cov', 5))
+    o.min_freq = float(kwargs.get('min_freq', .05))
+    o.min_snp = int(kwargs.get('min_snp', 10))
+    # the CLI always passes its own default of 50 (argumentParser.py:170); profile_split's fallback of 5 (:143) is never reached from it
+    o.rarefied = int(kwargs.get('rarefied_coverage', 50))
+    o.seed = int(kwargs.get('seed', 0))
+    o.store_everything = bool(kwargs.get('store_everything', False))
+    o.strict = bool(kwargs.get('strict'))
+    o.device = int(kwargs.get('device', 0))
+    o.host_threads = int(kwargs.get('host_threads', 0))
+    # pass 1 (inflate + record walk) may run on another number of threads than the hand-over
+    # (2 x host_threads measured both ways box to box in round 6: 180 -> 137 ms once, 155 -> 180 ms another time; the caller may choose)
+    o.scan_threads = int(kwargs.get('scan_threads', o.host_threads))
+    o.batch_positions = int(kwargs.get('batch_positions', 64_000_000))
+    if 'batch_reads' in kwargs:
+        o.batch_segs = int(kwargs['batch_reads'])
+    else:
+        o.batch_segs = max(64, int(kwargs['batch_observations']) // 150) if 'batch_observations' in kwargs else 4_000_000
+    o.pipe_depth, o.layout, o.jump_slack = kwargs.get('pipe_depth'), kwargs.get('layout'), kwargs.get('jump_slack')
+    o.filter = read_filter_flags(kwargs)
+    # what only a caller that shares the file's scan hands over (dist.profile_bam_sharded)
+    o.scan_part, o.median_insert, o.filter_refs = kwargs.get('scan_part'), kwargs.get('median_insert'), kwargs.get('filter_refs')
+    o.priority_reads = kwargs.get('priority_reads')
+    return o
+
+
+def select_scaffolds(refs, s2s, fasta_db, window_length, bam):
+    """Which scaffolds can be profiled at all.  refs: the BAM header's (name, length, ...) rows; fasta_db decides which are wanted
+    (without it every reference that has a sequence).  -> plan = [(tid, name, [(split_number, start, end), ...])] in file order (the
+    stream stays position-clustered), failed = {name: (exception, number of failure lines)}"""
+    tid_of = {n: i for i, (n, _, _) in enumerate(refs)}
+    if fasta_db is not None:
+        wanted = list(dict.fromkeys(fasta_db['scaffold'].values.tolist()))
+        rows_of = fasta_db['scaffold'].value_counts(sort=False).to_dict()
+    else:
+        wanted = [n for n, _, _ in refs if n in s2s]
+        rows_of = {}
+    usable, failed = {}, {}
+    for name in wanted:
+        if name not in tid_of:                   # samfile.pileup raises ValueError -> (None, log) (profile_utilities.py:154-156)
+            failed[name] = ValueError("scaffold {0} is not in the .bam file {1}!".format(name, bam))
+        elif name not in s2s or len(s2s[name]) != refs[tid_of[name]][1]:
+            failed[name] = ValueError("scaffold {0} has no sequence / its length differs from the .bam header".format(name))
+        else:
+            usable[name] = refs[tid_of[name]][1]
+    splits_of, bad = plan_scaffolds(fasta_db, usable, window_length)
+    failed.update(bad)
+    plan = sorted((tid_of[name], name, sp) for name, sp in splits_of.items())
+    return plan, {name: (e, int(rows_of.get(name, 1))) for name, e in failed.items()}
+
+
+def choose_read_pairs(bf, plan, n_refs, sR2M, opt):
+    """Which read pairs of the scanned file count, and with which mm: the controller's R2M, or the built-in filter"""
+    if sR2M is None:
+        if opt.priority_reads:
+            bf.set_priority_reads(opt.priority_reads)
+        # the reference's filter only ever sees the scaffolds of the fasta (filter_reads.py:63-77): a BAM mapped to a larger
+        # database must not let the other references into the median insert / the cross-scaffold look-ups
+        wanted_tids = opt.filter_refs
+        if wanted_tids is None:
+            wanted_tids = [t for t, _, _ in plan] if len(plan) < n_refs else []
+        bf.set_wanted_refs(wanted_tids)
+        bf.filter(median_insert=opt.median_insert, **opt.filter)
+        return
+    for tid, name, _ in plan:
+        r2m = sR2M.get(name, {})
+        if isinstance(r2m, (set, frozenset, list, tuple)):       # --skip_mm_profiling: a set of pair names
+            bf.set_r2m(tid, list(r2m), None)
+        else:
+            bf.set_r2m(tid, list(r2m.keys()), [0 if opt.skip_mm else int(v) for v in r2m.values()])
+    bf.scan(part=opt.scan_part)                  # refresh the totals (max_mm now comes from the controller's values)
+
+
+def mm_levels(bf, skip_mm, strict):
+    """The mm levels the kept pairs travel with -> n_mm (bins of a device batch), mm_values (None, or rank -> the pairs' mm), mm_clamped
+    (None, or the mm the pairs beyond the 128th level are counted at)"""
+    n_mm = 1 if skip_mm else int(bf.info["max_mm"]) + 1
+    mm_clamped = None
+    mm_values = None
+    bf.set_mm_levels([])
+    bf.set_mm_cap(0x7FFFFFFF)
+    if n_mm > 128:
+        # the reference bins any mm (profile_utilities.py:268-286); a device batch indexes 128 levels.  Every table depends on the
+        # ORDER of the levels alone (counts are cumulated over the levels <= mm, :297-312), so the pairs travel with the RANK of
+        # their mm among the values that occur and the tables' levels are mapped back (round 6: exact for any mm as long as no
+        # more than 128 DIFFERENT values occur among the kept pairs)
+        mm_values = np.asarray(bf.mm_levels(), dtype=np.int64)
+        bf.set_mm_levels(mm_values)
+        n_mm = len(mm_values)
+        if n_mm > 128:
+            # more than 128 different values: the pairs beyond the 128th are piled up AT it (their bases then appear early in the
+            # cumulative tables of the levels from there on) -- loudly, on every SplitObject (S.mm_clamped = that value), and never
+            # under strict=True: a caller that asked for exactness gets the error instead of merged levels
+            if strict:
+                raise ValueError("read pairs with {0} different numbers of mismatches (up to {1}): the device bins 128 mm levels "
+                                 "(strict=True refuses to merge the levels beyond; --skip_mm_profiling or a higher --min_read_ani "
+                                 "avoids this)".format(n_mm, int(mm_values[-1])))
+            mm_clamped = int(mm_values[127])
+            logging.warning("read pairs with {0} different numbers of mismatches: the device bins 128 mm levels, pairs beyond {1} "
+                            "mismatches are counted at that level (--skip_mm_profiling or a higher --min_read_ani avoids "
+                            "this)".format(n_mm, mm_clamped))
+            bf.set_mm_cap(127)
+            mm_values = mm_values[:128]
+            n_mm = 128
+    return n_mm, mm_values, mm_clamped
+
+
+def estimate_segments(info, reads_per_ref, plan):
+    """Read segments every scaffold of the plan will be: a read = one segment per 150 aligned columns (2 x 250 / 2 x 300 libraries: two
+    or more) + one per indel; the mean read length comes from the filter's tallies in `info` (sum of the kept pairs' query lengths,
+    controller.py:309-310)"""
+    fp, fb = int(info.get("filtered_pairs", 0) or 0), int(info.get("filtered_bases", 0) or 0)
+    mean_len = fb / (2.0 * fp) if fp > 0 and fb > 0 else 150.0
+    per_read = float(-(-int(np.ceil(mean_len)) // 150)) + 0.25
+    return [int(reads_per_ref[tid] * per_read) + 64 for tid, _, _ in plan]
+
+
+def largest_need(item_groups, plan, refs, est_segs):
+    """(positions, segments, splits) a pipe must hold for the largest group: it follows from the plan alone"""
+    return (max(sum(refs[plan[k][0]][1] for k in items) for items in item_groups),
+            max(sum(est_segs[k] for k in items) for items in item_groups),
+            max(sum(len(plan[k][2]) for k in items) + 1 for items in item_groups))
+
+
+def pipe_depth_of(opt, n_groups):
+    """device batches in flight"""
+    return max(1, int((2 if n_groups > 1 else 1) if opt.pipe_depth is None else opt.pipe_depth))
+
+
+def open_pipe(ctx, opt, n_mm, depth, need):
+    """The read-level pipe of a run for batches of up to `need` = (positions, segments, splits); pipe.cap = what it was made with"""
+    cap = (max(need[0], 1 << 16), max(need[1], 1 << 12), max(need[2], 64))
+    pp = engine.Pipe(ctx, max_pos=cap[0], max_obs=0, max_segs=cap[1], max_splits=cap[2], depth=depth,
+                     host_threads=opt.host_threads, pin_threads=False,
+                     min_cov=opt.min_cov, min_freq=opt.min_freq, min_snp=opt.min_snp,
+                     rarefied_coverage=opt.rarefied, n_mm_bins=n_mm,
+                     enable_linkage=True, seed=opt.seed, want_counts=opt.store_everything,
+                     # mm profiling on: the front end emits bit planes + the pairs' levels, the batches travel as 32-byte
+                     # reference-delta records with the level in the header (round 6) -- half the bytes, the 14-ns stager
+                     layout=int((_lib.LAYOUT_MM_DELTA_RECORDS if n_mm > 1 else 0) if opt.layout is None else opt.layout),
+                     # (a read that differs from the reference at more than three columns is several delta records: pairs kept at
+                     # 95 % identity carry up to 15 mismatches -- room for their pieces)
+                     jump_slack=float((1.0 if n_mm > 1 else 0.0) if opt.jump_slack is None else opt.jump_slack))
+    pp.cap = cap
+    return pp
+
+
+def _encode_scaffold(seq):
+    return engine.encode_seq(str(seq).upper())
+
+
+class _StageClock:
+    """stats[name] += the milliseconds since the last stamp (profile_bam's `stats`; nothing without one)"""
+
+    def __init__(self, stats):
+        self.stats, self.t = stats, time.perf_counter()
+
+    def __call__(self, name):
+        if self.stats is not None:
+            now = time.perf_counter()
+            self.stats[name] = self.stats.get(name, 0.0) + (now - self.t) * 1e3
+            self.t = now
+
+
 class _Group:
     """one device batch of whole scaffolds: its flat layout"""
     __slots__ = ("items", "tids", "bounds", "s_scaff", "s_num", "s_off", "s_len", "ref", "n_pos", "first_split", "ticket", "est_segs", "t_submit", "pair_names")
+
+
+class _BatchRun:
+    """profile_bam's batch loop: groups of whole scaffolds go through a pipe, at most `depth` in flight, collected in submission order
+    into `out`.  A group the pipe is too small for gets a larger pipe (grow_and_submit); a group whose batch fails is profiled scaffold by
+    scaffold so that only the offender is dropped (run_alone).  The pipe comes from `make_pipe(need)`; every ticket is collected and
+    released on the pipe that issued it -- the pipe is only replaced while nothing is in flight."""
+
+    def __init__(self, bf, plan, refs, opt, make_pipe, depth, codes_of, est_segs, out, stage, bam=None, mm_values=None, mm_clamped=None,
+                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None):
+        self.bf, self.plan, self.refs, self.opt, self.make_pipe, self.depth = bf, plan, refs, opt, make_pipe, depth
+        self.codes_of, self.est_segs, self.out, self.stage, self.bam = codes_of, est_segs, out, stage, bam
+        self.mm_values, self.mm_clamped, self.gset, self.logs = mm_values, mm_clamped, gset, logs
+        self.scaffold_tables, self.scaffold_levels = scaffold_tables, scaffold_levels
+        self.ekw = dict(opt.filter, skip_mm=opt.skip_mm, window_length=opt.window_length)
+        self.pipe = self.cap = None
+        self.in_flight = []                          # submitted, not yet collected (at most `depth`)
+
+    def open_pipe(self, need):
+        self.pipe = self.make_pipe(need)
+        self.cap = need
+
+    def layout(self, items):
+        g = _Group()
+        g.items, g.tids = items, [self.plan[k][0] for k in items]
+        bounds, g.s_scaff, g.s_num, g.s_off, g.s_len, g.first_split = split_table(
+            (self.plan[k][1], self.refs[self.plan[k][0]][1], self.plan[k][2]) for k in items)
+        seqs = [self.codes_of[k].result() for k in items]
+        g.bounds = np.asarray(bounds, np.int64)
+        g.ref = np.concatenate(seqs) if len(seqs) > 1 else seqs[0]
+        g.n_pos = bounds[-1]
+        g.est_segs = sum(self.est_segs[k] for k in items)
+        g.ticket = g.t_submit = g.pair_names = None
+        return g
+
+    def submit(self, g):
+        """the front end's pass 2 for the group's scaffolds + hand-over; returns False when the pipe is too small"""
+        try:
+            g.ticket = self.pipe.submit_bam(self.bf, g.tids, g.ref, g.bounds, **self.ekw)
+            g.t_submit = time.time()
+            if self.opt.store_everything:
+                g.pair_names = self.bf.batch_pair_names()
+            return True
+        except engine.IsxError as e:
+            if e.code != _lib.ERR_CAPACITY:
+                raise
+            if os.environ.get("ISX_PROFILE_DEBUG"):
+                print("submit_bam:", e)
+            return False
+
+    def grow_and_submit(self, g, floor, base):
+        """The pipe was too small for g (the estimate was short: many indels / long reads, reads that are many records each), and nothing
+        is in flight: up to three larger pipes, 2 / 8 / 32 x `base` segments -- always of the base, never of an already grown value -- and
+        at least what the front end counted on the attempt before, nowhere below `floor` = (positions, segments, splits).  -> did it fit"""
+        for factor in (2, 8, 32):
+            n_real = int((self.bf.info or {}).get("n_segs", 0))
+            need = (max(floor[0], g.n_pos), max(factor * base, n_real + 4096), max(floor[2], len(g.bounds)))
+            self.pipe.close()
+            self.open_pipe(need)
+            if self.submit(g):
+                return True
+        return False
+
+    def collect(self, g):
+        """tables of a submitted group -> SplitObjects"""
+        t, opt = g.ticket, self.opt
+        try:
+            res = self.pipe.collect(t, rare_list=False, densify=False, shrunk_entries=not opt.store_everything)
+            self.stage("collect_wait_ms")
+            if "_result" in res:                    # mm profiling on: own copies of the level-sparse tables (1-3 bytes a level); the columns the
+                res["level_tables"] = self.pipe.levels_copy(res)     # splits' covT / clonT / clonTR are cut from are made on first access
+            if opt.store_everything:                # read_to_snvs / mm_to_position_graph of the splits are made from these
+                res["allele_obs"] = res["slot"].fetch_allele_obs()
+                res["pair_names"] = g.pair_names
+            splits = tables_to_splits(res, g.bounds, g.s_scaff, g.s_num, g.s_off, g.s_len, opt.min_freq, self.bam,
+                                      min_cov=opt.min_cov, started=g.t_submit, mm_clamped=self.mm_clamped, mm_values=self.mm_values)
+            summaries = self.scaffold_tables is not None or self.scaffold_levels is not None
+            genes = self.gset is not None and bool(splits)
+            if summaries or genes:
+                sb = np.r_[0, np.cumsum([self.refs[tid][1] for tid in g.tids])]
+                if summaries:
+                    self.summarize(g, res["slot"], splits, sb)
+                if genes:
+                    self.profile_genes(g, res["slot"], splits, sb)
+        finally:
+            self.pipe.release(t)
+            g.ticket = None
+        return splits
+
+    def summarize(self, g, slot, splits, sb):
+        """scaffold_levels / scaffold_tables of the group's scaffolds from the device summaries"""
+        levels, _ = slot.summarize(sb)
+        if self.mm_values is not None:              # the device's levels are ranks: back to the pairs' mm
+            for lv in levels:
+                lv['mm'] = self.mm_values[lv['mm'].astype(np.int64)]
+        tables = splits[0]._src[0] if splits else None
+        for j, k in enumerate(g.items):
+            tid, name, _ = self.plan[k]
+            if self.scaffold_levels is not None:    # the device's per-(scaffold, mm) aggregates as they are
+                self.scaffold_levels[name] = levels[j][levels[j]['present'] != 0].copy()
+            if self.scaffold_tables is not None:
+                snp = tables.snp_table(g.first_split[j], g.first_split[j + 1])     # the scaffold's rows in one cut
+                self.scaffold_tables[name] = make_coverage_table(levels[j], self.refs[tid][1], name, snp)
+
+    def profile_genes(self, g, slot, splits, sb):
+        """profile_genes_from_profile of every scaffold of the batch (gene_profile.py)"""
+        src = splits[0]._src[0]
+        names = [self.plan[k][1] for k in g.items]
+        snv = [_parse_Sdb(_make_snp_table(src.snp_table(g.first_split[j], g.first_split[j + 1]))) for j in range(len(names))]
+        snv = [d for d in snv if len(d)]
+        snv = pd.concat([d.astype({'scaffold': object, 'con_base': object}) for d in snv]) if snv else pd.DataFrame()
+        gl = []
+        gt = gene_profile.profile_batch(slot, self.gset, names, sb, snv, self.mm_values, gl)
+        for line in gl:
+            line = "\n{1} {0}".format(line, time.strftime('%m-%d %H:%M'))
+            logging.error(line)
+            if self.logs is not None:
+                self.logs.append(line)
+        for kk in gene_profile.TABLE_NAMES:
+            self.gset.tables[kk].append(gt[kk])
+
+    def take(self, splits):
+        if not splits:
+            return
+        src = splits[0].__dict__.get('_src')
+        if src is not None and all(S.__dict__.get('_src') is not None and S.__dict__['_src'][0] is src[0] for S in (splits[0], splits[-1])):
+            m = src[0].meta                         # (the keys straight from the batch's split table: no per-object field is realised)
+            self.out.update(zip(map("{0}.{1}".format, m['scaffold'], m['number']), splits))
+        else:                                       # materialised / unpickled objects: their own fields
+            self.out.update(("{0}.{1}".format(S.scaffold, S.split_number), S) for S in splits)
+
+    def run_alone(self, items):
+        """a group whose batch failed: scaffold by scaffold, so that only the offender is dropped (nothing is in flight)"""
+        for k in items:
+            try:
+                g = self.layout([k])
+                if not self.submit(g) and not self.grow_and_submit(g, (0, 0, 0), g.est_segs):
+                    raise RuntimeError("scaffold does not fit a device batch")
+                self.take(self.collect(g))
+            except Exception as e2:
+                _fail(self.logs, self.plan[k][1], [sp[0] for sp in self.plan[k][2]], e2)
+
+    def drain_one(self):
+        g = self.in_flight.pop(0)
+        try:
+            sp = self.collect(g)
+            self.stage("collect_ms")
+            self.take(sp)
+        except Exception as e:
+            print(e)
+            traceback.print_exc()
+            failed = [g]                            # run_alone may replace the pipe: bring every other batch home on this one first
+            while self.in_flight:
+                h = self.in_flight.pop(0)
+                try:
+                    self.take(self.collect(h))
+                except Exception:
+                    failed.append(h)
+            for h in failed:
+                self.run_alone(h.items)
+
+    def drain(self):
+        while self.in_flight:
+            self.drain_one()
+
+    def run(self, item_groups, layouts):
+        """layouts[i]: the future of item_groups[i]'s _Group; dropped once used"""
+        for gi, items in enumerate(item_groups):
+            while len(self.in_flight) >= self.depth:
+                self.drain_one()
+            try:
+                g = layouts[gi].result()
+                layouts[gi] = None
+                self.stage("layout_wait_ms")
+                ok = self.submit(g)
+                self.stage("submit_ms")
+                if not ok:
+                    self.drain()                    # a larger pipe once the batches in flight are home
+                    if not self.grow_and_submit(g, self.cap, self.cap[1]):
+                        raise RuntimeError("batch does not fit the device pipe")
+                self.in_flight.append(g)
+            except Exception as e:
+                print(e)
+                traceback.print_exc()
+                self.drain()
+                self.run_alone(items)
+        self.drain()
 
 
 def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
@@ -699,68 +1089,25 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     The BAM's reads go to the device as read segments (isx_pipe_submit_bam on a read-level pipe): the host never expands a
     read into per-base records.
     Returns {"scaffold.split": SplitObject} = Sprofile_dict (profile_utilities.py:85)."""
-    s2s = kwargs['s2s']
-    null_model = kwargs['null_model']
-    logs = kwargs.get('logs')
-    stats = kwargs.get('stats')
-    W = int(kwargs.get('window_length', 10000))
-    skip_mm = bool(kwargs.get('skip_mm_profiling', False))
-    min_freq = float(kwargs.get('min_freq', .05))
-    store_everything = bool(kwargs.get('store_everything', False))
-    # the CLI always passes its own default of 50 (argumentParser.py:170); profile_split's fallback of 5 (:143) is never reached from it
-    rarefied = int(kwargs.get('rarefied_coverage', 50))
+    s2s, null_model, logs = kwargs['s2s'], kwargs['null_model'], kwargs.get('logs')
+    opt = profile_options(kwargs)
     out = {}
-    t_stage = [time.perf_counter()]
-
-    def stage(name):
-        if stats is not None:
-            now = time.perf_counter()
-            stats[name] = stats.get(name, 0.0) + (now - t_stage[0]) * 1e3
-            t_stage[0] = now
-
-    def fail(scaffold, split_numbers, exc=None):
-        if exc is not None:
-            print(exc)
-            traceback.print_exc()
-        for n in split_numbers:
-            line = _failure_log(scaffold, n)
-            logging.error(line)
-            if logs is not None:
-                logs.append(line)
-
+    stage = _StageClock(kwargs.get('stats'))
     own_ctx = kwargs.get('ctx') is None
     own_bf = kwargs.get('bamfile') is None           # a caller's handle may already hold the scan (dist.profile_bam_sharded)
-    ctx = bf = pipe = helpers = gset = None
+    ctx = bf = run = helpers = gset = None
+    codes_of, layouts = [], []
     if kwargs.get('genes') is None and kwargs.get('gene_file'):        # a gene file the run cannot use is the caller's error, not a split's
         kwargs['genes'] = gene_profile.parse_genes(kwargs['gene_file'])
     try:
-        ctx = kwargs.get('ctx') or engine.Context(int(kwargs.get('device', 0)))
-        lut, fb = null_model_lut(null_model)
-        ctx.set_null_model(lut, fb)
+        ctx = kwargs.get('ctx') or engine.Context(opt.device)
+        ctx.set_null_model(*null_model_lut(null_model))
         gset = gene_profile.start_genes(ctx, kwargs)
-        bf = kwargs.get('bamfile') or engine.BamFile(bam, threads=int(kwargs.get('host_threads', 0)))
+        bf = kwargs.get('bamfile') or engine.BamFile(bam, threads=opt.host_threads)
         refs = bf.refs()
-        tid_of = {n: i for i, (n, _, _) in enumerate(refs)}
-        if fasta_db is not None:
-            wanted = list(dict.fromkeys(fasta_db['scaffold'].values.tolist()))
-            rows_of = fasta_db['scaffold'].value_counts(sort=False).to_dict()
-        else:
-            wanted = [n for n, _, _ in refs if n in s2s]
-            rows_of = {}
-        # ---- which scaffolds can be profiled at all ----
-        usable, failed = {}, {}
-        for name in wanted:
-            if name not in tid_of:                   # samfile.pileup raises ValueError -> (None, log) (profile_utilities.py:154-156)
-                failed[name] = ValueError("scaffold {0} is not in the .bam file {1}!".format(name, bam))
-            elif name not in s2s or len(s2s[name]) != refs[tid_of[name]][1]:
-                failed[name] = ValueError("scaffold {0} has no sequence / its length differs from the .bam header".format(name))
-            else:
-                usable[name] = refs[tid_of[name]][1]
-        splits_of, bad = plan_scaffolds(fasta_db, usable, W)
-        failed.update(bad)
-        for name, e in failed.items():
-            fail(name, range(int(rows_of.get(name, 1))), e)
-        plan = sorted((tid_of[name], name, sp) for name, sp in splits_of.items())     # file order: the stream stays position-clustered
+        plan, failed = select_scaffolds(refs, s2s, fasta_db, opt.window_length, bam)
+        for name, (e, n_lines) in failed.items():
+            _fail(logs, name, range(n_lines), e)
         stage("plan_ms")
         if not plan:
             return out
@@ -768,279 +1115,36 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
         # the GIL); the same helpers later set the pipe up and lay the groups out
         from concurrent.futures import ThreadPoolExecutor
         helpers = ThreadPoolExecutor(2)
-        codes_of = [helpers.submit(lambda nm=name: engine.encode_seq(str(s2s[nm]).upper())) for _, name, _ in plan]
-        # ---- read pairs: the controller's R2M, or the built-in filter ----
-        # pass 1 (inflate + record walk) may run on another number of threads than the hand-over (scan_threads)
-        n_thr = int(kwargs.get('host_threads', 0))
-        scan_thr = int(kwargs.get('scan_threads', n_thr))       # (2 x n_thr measured both ways box to box in round 6: 180 -> 137 ms once, 155 -> 180 ms another time; the caller may choose)
-        if own_bf and n_thr > 0 and scan_thr != n_thr:
-            bf.set_threads(scan_thr)
-        bf.scan(part=kwargs.get('scan_part'))
+        codes_of.extend(helpers.submit(_encode_scaffold, s2s[name]) for _, name, _ in plan)
+        switch_threads = own_bf and opt.host_threads > 0 and opt.scan_threads != opt.host_threads
+        if switch_threads:
+            bf.set_threads(opt.scan_threads)
+        bf.scan(part=opt.scan_part)
         stage("scan_ms")
-        fkw = dict(min_read_ani=kwargs.get('min_read_ani', 0.95), min_mapq=kwargs.get('min_mapq', -1),
-                   max_insert_relative=kwargs.get('max_insert_relative', 3), min_insert=kwargs.get('min_insert', 50),
-                   pairing_filter=kwargs.get('pairing_filter', 'paired_only'))
-        ekw = dict(fkw, skip_mm=skip_mm, window_length=W)
-        if sR2M is None:
-            if kwargs.get('priority_reads'):
-                bf.set_priority_reads(kwargs['priority_reads'])
-            # the reference's filter only ever sees the scaffolds of the fasta (filter_reads.py:63-77): a BAM mapped to a larger
-            # database must not let the other references into the median insert / the cross-scaffold look-ups
-            wanted_tids = kwargs.get('filter_refs')
-            if wanted_tids is None:
-                wanted_tids = [t for t, _, _ in plan] if len(plan) < len(refs) else []
-            bf.set_wanted_refs(wanted_tids)
-            bf.filter(median_insert=kwargs.get('median_insert'), **fkw)
-        else:
-            for tid, name, _ in plan:
-                r2m = sR2M.get(name, {})
-                if isinstance(r2m, (set, frozenset, list, tuple)):       # --skip_mm_profiling: a set of pair names
-                    bf.set_r2m(tid, list(r2m), None)
-                else:
-                    bf.set_r2m(tid, list(r2m.keys()), [0 if skip_mm else int(v) for v in r2m.values()])
-            bf.scan(part=kwargs.get('scan_part'))    # refresh the totals (max_mm now comes from the controller's values)
-        n_mm = 1 if skip_mm else int(bf.info["max_mm"]) + 1
-        mm_clamped = None
-        mm_values = None
-        bf.set_mm_levels([])
-        bf.set_mm_cap(0x7FFFFFFF)
-        if n_mm > 128:
-            # the reference bins any mm (profile_utilities.py:268-286); a device batch indexes 128 levels.  Every table depends on the
-            # ORDER of the levels alone (counts are cumulated over the levels <= mm, :297-312), so the pairs travel with the RANK of
-            # their mm among the values that occur and the tables' levels are mapped back (round 6: exact for any mm as long as no
-            # more than 128 DIFFERENT values occur among the kept pairs)
-            mm_values = np.asarray(bf.mm_levels(), dtype=np.int64)
-            bf.set_mm_levels(mm_values)
-            n_mm = len(mm_values)
-            if n_mm > 128:
-                # more than 128 different values: the pairs beyond the 128th are piled up AT it (their bases then appear early in the
-                # cumulative tables of the levels from there on) -- loudly, on every SplitObject (S.mm_clamped = that value), and never
-                # under strict=True: a caller that asked for exactness gets the error instead of merged levels
-                if kwargs.get('strict'):
-                    raise ValueError("read pairs with {0} different numbers of mismatches (up to {1}): the device bins 128 mm levels "
-                                     "(strict=True refuses to merge the levels beyond; --skip_mm_profiling or a higher --min_read_ani "
-                                     "avoids this)".format(n_mm, int(mm_values[-1])))
-                mm_clamped = int(mm_values[127])
-                logging.warning("read pairs with {0} different numbers of mismatches: the device bins 128 mm levels, pairs beyond {1} "
-                                "mismatches are counted at that level (--skip_mm_profiling or a higher --min_read_ani avoids "
-                                "this)".format(n_mm, mm_clamped))
-                bf.set_mm_cap(127)
-                mm_values = mm_values[:128]
-                n_mm = 128
-        reads_per_ref, pairs_per_ref = bf.ref_counts()
-        if not store_everything:                    # (--store_everything keys read_to_snvs by read name: the names stay)
+        choose_read_pairs(bf, plan, len(refs), sR2M, opt)
+        n_mm, mm_values, mm_clamped = mm_levels(bf, opt.skip_mm, opt.strict)
+        reads_per_ref, _ = bf.ref_counts()
+        if not opt.store_everything:                # (--store_everything keys read_to_snvs by read name: the names stay)
             bf.drop_names()
-        if own_bf and n_thr > 0 and scan_thr != n_thr:
-            bf.set_threads(n_thr)
+        if switch_threads:
+            bf.set_threads(opt.host_threads)
         stage("filter_ms")
-        # ---- batches of whole scaffolds under a position / read budget; the reference groups its commands by estimated
-        #      cost the same way (profile_controller.py:436-457) ----
-        # a read = one segment per 150 aligned columns (2 x 250 / 2 x 300 libraries: two or more) + one per indel; the mean read
-        # length comes from the filter's tallies (sum of the kept pairs' query lengths, controller.py:309-310)
-        fp, fb = int(bf.info.get("filtered_pairs", 0) or 0), int(bf.info.get("filtered_bases", 0) or 0)
-        mean_len = fb / (2.0 * fp) if fp > 0 and fb > 0 else 150.0
-        per_read = float(-(-int(np.ceil(mean_len)) // 150)) + 0.25
-        est_segs = [int(reads_per_ref[tid] * per_read) + 64 for tid, _, _ in plan]
-        max_pos = int(kwargs.get('batch_positions', 64_000_000))
-        max_segs = int(kwargs.get('batch_reads', max(64, int(kwargs['batch_observations']) // 150) if 'batch_observations' in kwargs else 4_000_000))
-        item_groups = idist.pack_batches([refs[tid][1] for tid, _, _ in plan], est_segs, max_pos, max_segs)
-
-        def layout(items):
-            g = _Group()
-            g.items, g.tids = items, [plan[k][0] for k in items]
-            bounds, s_scaff, s_num, s_off, s_len, seqs, first_split = [], [], [], [], [], [], []
-            off = 0
-            for k in items:
-                tid, name, splits = plan[k]
-                first_split.append(len(bounds))
-                for (num, s, e) in splits:
-                    bounds.append(off + s)
-                    s_scaff.append(name); s_num.append(num); s_off.append(off); s_len.append(e - s + 1)
-                seqs.append(codes_of[k].result())
-                off += refs[tid][1]
-            first_split.append(len(bounds))
-            bounds.append(off)
-            g.bounds, g.s_scaff, g.s_num, g.s_off, g.s_len = np.asarray(bounds, np.int64), s_scaff, s_num, s_off, s_len
-            g.ref = np.concatenate(seqs) if len(seqs) > 1 else seqs[0]
-            g.n_pos, g.first_split = off, first_split
-            g.est_segs = sum(est_segs[k] for k in items)
-            g.ticket = None
-            return g
-
-        depth = max(1, int(kwargs.get('pipe_depth', 2 if len(item_groups) > 1 else 1)))
-
-        def make_pipe(need):
-            cap = (max(need[0], 1 << 16), max(need[1], 1 << 12), max(need[2], 64))
-            pp = engine.Pipe(ctx, max_pos=cap[0], max_obs=0, max_segs=cap[1], max_splits=cap[2], depth=depth,
-                             host_threads=int(kwargs.get('host_threads', 0)), pin_threads=False,
-                             min_cov=int(kwargs.get('min_cov', 5)), min_freq=min_freq, min_snp=int(kwargs.get('min_snp', 10)),
-                             rarefied_coverage=rarefied, n_mm_bins=n_mm,
-                             enable_linkage=True, seed=int(kwargs.get('seed', 0)), want_counts=store_everything,
-                             # mm profiling on: the front end emits bit planes + the pairs' levels, the batches travel as 32-byte
-                             # reference-delta records with the level in the header (round 6) -- half the bytes, the 14-ns stager
-                             layout=int(kwargs.get('layout', _lib.LAYOUT_MM_DELTA_RECORDS if n_mm > 1 else 0)),
-                             # (a read that differs from the reference at more than three columns is several delta records: pairs kept at
-                             # 95 % identity carry up to 15 mismatches -- room for their pieces)
-                             jump_slack=float(kwargs.get('jump_slack', 1.0 if n_mm > 1 else 0.0)))
-            pp.cap = cap
-            return pp
-
-        def submit(g):
-            """the front end's pass 2 for the group's scaffolds + hand-over; returns False when the pipe is too small"""
-            try:
-                g.ticket = pipe.submit_bam(bf, g.tids, g.ref, g.bounds, **ekw)
-                g.t_submit = time.time()
-                if store_everything:
-                    g.pair_names = bf.batch_pair_names()
-                return True
-            except engine.IsxError as e:
-                if e.code != -3:
-                    raise
-                if os.environ.get("ISX_PROFILE_DEBUG"):
-                    print("submit_bam:", e)
-                return False
-
-        def collect(g):
-            """tables of a submitted group -> SplitObjects"""
-            t = g.ticket
-            try:
-                res = pipe.collect(t, rare_list=False, densify=False, shrunk_entries=not store_everything)
-                stage("collect_wait_ms")
-                if "_result" in res:                # mm profiling on: own copies of the level-sparse tables (1-3 bytes a level); the columns the
-                    res["level_tables"] = pipe.levels_copy(res)      # splits' covT / clonT / clonTR are cut from are made on first access
-                if store_everything:                # read_to_snvs / mm_to_position_graph of the splits are made from these
-                    res["allele_obs"] = res["slot"].fetch_allele_obs()
-                    res["pair_names"] = getattr(g, 'pair_names', None)
-                splits = tables_to_splits(res, g.bounds, g.s_scaff, g.s_num, g.s_off, g.s_len, min_freq, bam,
-                                          min_cov=int(kwargs.get('min_cov', 5)), started=getattr(g, 't_submit', None), mm_clamped=mm_clamped, mm_values=mm_values)
-                if kwargs.get('scaffold_tables') is not None or kwargs.get('scaffold_levels') is not None:
-                    sb = np.r_[0, np.cumsum([refs[tid][1] for tid in g.tids])]
-                    levels, _ = res["slot"].summarize(sb)
-                    if mm_values is not None:               # the device's levels are ranks: back to the pairs' mm
-                        for lv in levels:
-                            lv['mm'] = mm_values[lv['mm'].astype(np.int64)]
-                    tables = splits[0]._src[0] if splits else None
-                    for j, k in enumerate(g.items):
-                        name = plan[k][1]
-                        if kwargs.get('scaffold_levels') is not None:       # the device's per-(scaffold, mm) aggregates as they are
-                            kwargs['scaffold_levels'][name] = levels[j][levels[j]['present'] != 0].copy()
-                        if kwargs.get('scaffold_tables') is not None:
-                            snp = tables.snp_table(g.first_split[j], g.first_split[j + 1])     # the scaffold's rows in one cut
-                            kwargs['scaffold_tables'][name] = make_coverage_table(levels[j], refs[plan[k][0]][1], name, snp)
-                if gset is not None and splits:             # profile_genes_from_profile of every scaffold of the batch (gene_profile.py)
-                    src = splits[0]._src[0]
-                    names = [plan[k][1] for k in g.items]
-                    sb = np.r_[0, np.cumsum([refs[tid][1] for tid in g.tids])]
-                    snv = [_parse_Sdb(_make_snp_table(src.snp_table(g.first_split[j], g.first_split[j + 1]))) for j in range(len(names))]
-                    snv = [d for d in snv if len(d)]
-                    snv = pd.concat([d.astype({'scaffold': object, 'con_base': object}) for d in snv]) if snv else pd.DataFrame()
-                    gl = []
-                    gt = gene_profile.profile_batch(res["slot"], gset, names, sb, snv, mm_values, gl)
-                    for line in gl:
-                        line = "\n{1} {0}".format(line, time.strftime('%m-%d %H:%M'))
-                        logging.error(line)
-                        if logs is not None:
-                            logs.append(line)
-                    for kk in gene_profile.TABLE_NAMES:
-                        gset.tables[kk].append(gt[kk])
-            finally:
-                pipe.release(t)
-                g.ticket = None
-            return splits
-
-        def take(splits):
-            if not splits:
-                return
-            src = splits[0].__dict__.get('_src')
-            if src is not None and all(S.__dict__.get('_src') is not None and S.__dict__['_src'][0] is src[0] for S in (splits[0], splits[-1])):
-                m = src[0].meta                     # (the keys straight from the batch's split table: no per-object field is realised)
-                out.update(zip(map("{0}.{1}".format, m['scaffold'], m['number']), splits))
-            else:                                   # materialised / unpickled objects: their own fields
-                out.update(("{0}.{1}".format(S.scaffold, S.split_number), S) for S in splits)
-
-        def run_alone(items):
-            """a group whose batch failed: scaffold by scaffold, so that only the offender is dropped"""
-            nonlocal pipe
-            for k in items:
-                try:
-                    g = layout([k])
-                    if not submit(g):
-                        ok = False
-                        for grow in (2, 8, 32):
-                            need = (g.n_pos, max(int(bf.info.get("n_segs", 0)) + 4096, grow * g.est_segs), len(g.bounds))
-                            pipe.close()
-                            pipe = make_pipe(need)
-                            ok = submit(g)
-                            if ok:
-                                break
-                        if not ok:
-                            raise RuntimeError("scaffold does not fit a device batch")
-                    take(collect(g))
-                except Exception as e2:
-                    fail(plan[k][1], [sp[0] for sp in plan[k][2]], e2)
-
-        # what the largest group needs follows from the plan alone; the pipe (pinned staging, device arena: tens of ms) is set
-        # up by one helper thread while another lays the groups out (sequence codes, split tables: Python + numpy) -- a group's
-        # layout is then ready when the group before it is being handed over (isx_pipe_submit_bam runs without the GIL)
-        need = (max(sum(refs[plan[k][0]][1] for k in items) for items in item_groups),
-                max(sum(est_segs[k] for k in items) for items in item_groups),
-                max(sum(len(plan[k][2]) for k in items) + 1 for items in item_groups))
-        pipe_f = helpers.submit(make_pipe, need)
-        layouts = [helpers.submit(layout, items) for items in item_groups]
-        pipe = pipe_f.result()
+        # batches of whole scaffolds under a position / read budget; the reference groups its commands by estimated cost the same
+        # way (profile_controller.py:436-457)
+        est_segs = estimate_segments(bf.info, reads_per_ref, plan)
+        item_groups = idist.pack_batches([refs[tid][1] for tid, _, _ in plan], est_segs, opt.batch_positions, opt.batch_segs)
+        depth = pipe_depth_of(opt, len(item_groups))
+        run = _BatchRun(bf, plan, refs, opt, functools.partial(open_pipe, ctx, opt, n_mm, depth), depth, codes_of, est_segs, out, stage,
+                        bam=bam, mm_values=mm_values, mm_clamped=mm_clamped, gset=gset, logs=logs,
+                        scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'))
+        # the pipe (pinned staging, device arena: tens of ms) is set up by one helper thread while another lays the groups out
+        # (sequence codes, split tables: Python + numpy) -- a group's layout is then ready when the group before it is being handed
+        # over (isx_pipe_submit_bam runs without the GIL)
+        pipe_f = helpers.submit(run.open_pipe, largest_need(item_groups, plan, refs, est_segs))
+        layouts.extend(helpers.submit(run.layout, items) for items in item_groups)
+        pipe_f.result()
         stage("setup_ms")
-        in_flight = []                               # submitted, not yet collected (at most `depth`)
-
-        def drain_one():
-            g = in_flight.pop(0)
-            try:
-                sp = collect(g)
-                stage("collect_ms")
-                take(sp)
-            except Exception as e:
-                print(e)
-                traceback.print_exc()
-                for h in in_flight:                  # the pipe may be rebuilt below: bring the others home first
-                    try:
-                        take(collect(h))
-                    except Exception:
-                        run_alone(h.items)
-                del in_flight[:]
-                run_alone(g.items)
-
-        for gi, items in enumerate(item_groups):
-            while len(in_flight) >= depth:
-                drain_one()
-            g = None
-            try:
-                g = layouts[gi].result()
-                layouts[gi] = None
-                stage("layout_wait_ms")
-                ok = submit(g)
-                stage("submit_ms")
-                if not ok:
-                    # the estimate was short (many indels / long reads): a larger pipe once the batches in flight are home
-                    while in_flight:
-                        drain_one()
-                    n_real = int(bf.info.get("n_segs", 0)) if bf.info else 0
-                    for grow in (2, 4, 8):              # (reads that are many records each: a few more tries before giving up)
-                        need = (max(need[0], g.n_pos), max(grow * need[1], n_real + 4096), max(need[2], len(g.bounds)))
-                        pipe.close()
-                        pipe = make_pipe(need)
-                        ok = submit(g)
-                        if ok:
-                            break
-                    if not ok:
-                        raise RuntimeError("batch does not fit the device pipe")
-                in_flight.append(g)
-            except Exception as e:
-                print(e)
-                traceback.print_exc()
-                while in_flight:
-                    drain_one()
-                run_alone(items)
-        while in_flight:
-            drain_one()
+        run.run(item_groups, layouts)
         if gset is not None:
             gene_profile.finish_genes(gset, kwargs['gene_tables'] if kwargs.get('gene_tables') is not None else {})
         return out
@@ -1048,7 +1152,7 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
         # a failure of the call as a whole (unreadable BAM, a pair beyond the 128 mm levels a device batch holds, a device fault):
         # the reference's convention is per split (profile_utilities.py:104-111) -- with strict=True the caller gets the exception
         # itself instead of a partial dict and one log line, so "the call failed" cannot be mistaken for "no reads"
-        if kwargs.get('strict'):
+        if opt.strict:
             raise
         print(e)
         traceback.print_exc()
@@ -1065,11 +1169,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
             gset.close()
         # this call's own large arrays (sequence codes, group layouts) go before the helper thread below starts unmapping the pipe's
         # and the handle's gigabytes: both want the process' address-space lock
-        try:
-            del codes_of[:], layouts[:]
-        except NameError:
-            pass
-        dead = [o for o in (pipe, bf if own_bf else None) if o is not None]
+        del codes_of[:], layouts[:]
+        dead = [o for o in (run.pipe if run is not None else None, bf if own_bf else None) if o is not None]
         if own_ctx and ctx is not None:
             for o in dead:
                 o.close()
