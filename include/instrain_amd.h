@@ -291,6 +291,54 @@ typedef struct {
 int isx_batch_summarize_genomes(isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, int32_t n_genomes,
                                 const int32_t *genome_first_scaffold, int32_t mask_edges, isx_genome_level *out, float *device_ms);
 
+/* ---- genome_info roll-ups (genomeUtilities.py:145-269 genomeLevel_from_IS): three per-batch passes whose results ADD, so a genome
+ * may be any subset of a batch's scaffolds and may span batches; the host merges them (profile/genome_utilities.py GenomeTables) ----
+ *
+ * (a) the masked coverage distribution of every genome (genomeLevel_coverage_info :297-365 on generate_genome_coverage_array
+ * :932-981).  Per mm level, on the coverage cumulated over levels <= mm: a position counts unless it lies within mask_edges of
+ * either end of its scaffold (a scaffold shorter than 2 * mask_edges drops out); a counted position adds to its genome's n, sum_cov
+ * and sumsq_cov (exact integers) and to hist[min(coverage, hist_bins - 1)]; max_cov = the largest counted coverage.  The histogram --
+ * and the median read from it -- is exact whenever max_cov < hist_bins; otherwise call again with more bins.  One pass over the
+ * positions per level, no sort. */
+typedef struct {
+    int64_t n;                      /* counted positions */
+    uint64_t sum_cov, sumsq_cov;
+    uint32_t max_cov, pad;
+} isx_genome_cov;
+
+/* scaffold_genome[n_scaffolds]: the genome 0..n_genomes-1 of each scaffold, in any order; -1 = in no genome.
+ * acc[n_genomes][n_mm_bins], hist[n_genomes][n_mm_bins][hist_bins] (hist_bins >= 2); both are overwritten.
+ * Needs a completed isx_batch_run; refused (ISX_ERR_STATE) on a lean pipe slot. */
+int isx_batch_genome_coverage(isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *scaffold_genome,
+                              int32_t n_genomes, int32_t mask_edges, int32_t hist_bins, isx_genome_cov *acc, uint32_t *hist,
+                              float *device_ms);
+
+/* (b) calc_snps (snv_utilities.py:249-272) for every (scaffold, level) at once, on host rows in (gpos, mm) order (a batch's fetched
+ * rows, or a stored table the caller laid out).  A row is current from its own mm up to the next row's mm at the same position
+ * (exclusive), or to n_levels; at each such level it counts into its scaffold: divergent always, sns when allele_count == 1, snv
+ * when allele_count > 1, con when cls is SNS / con_SNV / pop_SNV, pop when cls is SNS / pop_SNV. */
+typedef struct {
+    uint32_t divergent, sns, snv, con, pop;
+} isx_snv_level;
+
+/* out[n_scaffolds][n_levels]; every row's mm < n_levels; scaffold_bounds as for isx_batch_summarize, spanning the rows' flat space */
+int isx_snv_level_counts(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_snv, const isx_snv *snv,
+                         int32_t n_levels, isx_snv_level *out, float *device_ms);
+
+/* (c) the sums behind _genome_wide_linkage (genomeUtilities.py:636-659) for every (scaffold, level), on host rows in the order
+ * isx_batch_fetch_ld delivers: (gpos_a, gpos_b, mm).  A row is current from its mm up to the next row's mm of the same (gpos_a,
+ * gpos_b) -- the reference's drop_duplicates(keep='last') per level.  n counts every current row (linked_SNV_count); n_r2 / sum_r2
+ * and n_dprime / sum_dprime skip NaN values as Series.mean() does; sum_distance = sum of gpos_b - gpos_a.  One wave per
+ * (scaffold, level) sums in a fixed order, no floating-point atomics: two calls on the same rows return identical bytes. */
+typedef struct {
+    int64_t n, n_r2, n_dprime, sum_distance;
+    double sum_r2, sum_dprime;
+} isx_ld_level;
+
+/* out[n_scaffolds][n_levels]; a row belongs to the scaffold of its gpos_a */
+int isx_ld_level_sums(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_ld, const isx_ld *ld,
+                      int32_t n_levels, isx_ld_level *out, float *device_ms);
+
 /* ---- compare: two samples on the same scaffolds (readComparer.py:35-143 compare_scaffold, one pair) ----
  * Two batches over the SAME flat space (same scaffolds laid out identically, same ctx).  One row per
  * (scaffold, mm): positions where both / either sample reach min_cov in the coverage cumulated over

@@ -131,6 +131,11 @@ SCAFFOLD_LEVEL_DT = np.dtype([("nonzero", "<i8"), ("sum_cov", "<u8"), ("sumsq_co
 assert SCAFFOLD_LEVEL_DT.itemsize == 88
 GENOME_LEVEL_DT = np.dtype([("n", "<i8"), ("sum_cov", "<u8"), ("sumsq_cov", "<u8"), ("median_cov", "<f8"), ("mm", "<i4"), ("pad", "<i4")])
 assert GENOME_LEVEL_DT.itemsize == 40
+# genome_info roll-ups (include/instrain_amd.h isx_genome_cov / isx_snv_level / isx_ld_level)
+GENOME_COV_DT = np.dtype([("n", "<i8"), ("sum_cov", "<u8"), ("sumsq_cov", "<u8"), ("max_cov", "<u4"), ("pad", "<u4")])
+SNV_LEVEL_DT = np.dtype([(n, "<u4") for n in ("divergent", "sns", "snv", "con", "pop")])
+LD_LEVEL_DT = np.dtype([("n", "<i8"), ("n_r2", "<i8"), ("n_dprime", "<i8"), ("sum_distance", "<i8"), ("sum_r2", "<f8"), ("sum_dprime", "<f8")])
+assert GENOME_COV_DT.itemsize == 32 and SNV_LEVEL_DT.itemsize == 20 and LD_LEVEL_DT.itemsize == 48
 
 
 COMPARE_LEVEL_DT = np.dtype([("both", "<i8"), ("either", "<i8"), ("mm", "<i4"), ("present_a", "<i4"),
@@ -163,7 +168,7 @@ class IsxError(RuntimeError):
 SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destroy", "isx_ctx_reserve_cus", "isx_set_null_model",
            "isx_batch_create", "isx_batch_create_reads", "isx_batch_destroy", "isx_batch_run", "isx_batch_launch", "isx_batch_wait", "isx_batch_sizes", "isx_batch_timings",
            "isx_batch_fetch_entries", "isx_batch_fetch_dense", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs",
-           "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
+           "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
            "isx_genes_create", "isx_genes_destroy", "isx_genes_sites", "isx_batch_profile_genes", "isx_genes_profile_snvs",
            "isx_pipe_create", "isx_pipe_destroy", "isx_pipe_submit", "isx_pipe_submit_reads", "isx_pipe_stage_reads", "isx_pipe_submit_wire", "isx_wire_bytes", "isx_wire_free", "isx_wire_keep_reference", "isx_pipe_submit_bam", "isx_encode_segs", "isx_encode_segs_ring", "isx_seg_records_needed", "isx_encode_delta", "isx_delta_records_needed", "isx_count_read_segs", "isx_pack_reads", "isx_pipe_collect", "isx_pipe_release", "isx_pipe_fetch_entries", "isx_pipe_fetch_entries_shrunk", "isx_levels_expand", "isx_encode_obs", "isx_encode_obs_ring",
            "isx_pack_ref_planes", "isx_planes_from_segs", "isx_pack_read_planes", "isx_pipe_submit_planes", "isx_pipe_stage_planes", "isx_encode_planes", "isx_encode_planes_mm", "isx_pipe_set_reference_budget", "isx_host_register", "isx_host_unregister",
@@ -230,6 +235,9 @@ def load():
     lib.isx_batch_fetch_dense.argtypes = [vp, vp, vp, vp]
     lib.isx_batch_summarize.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_float)]
     lib.isx_batch_summarize_genomes.argtypes = [vp, i32, vp, i32, vp, i32, vp, C.POINTER(C.c_float)]
+    lib.isx_batch_genome_coverage.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_snv_level_counts.argtypes = [vp, i32, vp, i64, vp, i32, vp, C.POINTER(C.c_float)]
+    lib.isx_ld_level_sums.argtypes = [vp, i32, vp, i64, vp, i32, vp, C.POINTER(C.c_float)]
     lib.isx_compare_coverage.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(C.c_float)]
     lib.isx_compare_scaffolds.argtypes = [vp, vp, i32, vp, i32, C.c_double, vp, C.POINTER(i64), C.POINTER(C.c_float)]
     lib.isx_compare_fetch_snps.argtypes = [vp, vp]

@@ -1856,6 +1856,65 @@ int isx_genes_profile_snvs(isx_genes *g, int32_t n_scaffolds, const int64_t *sca
     return run_gene_snvs(g, n_scaffolds, scaffold_bounds, work, n_snv, snv, n_levels, mut_out, cnt_out, device_ms);
 }
 
+// ---- genome_info roll-ups (isx_genomes.hip) ----
+static int check_scaffold_bounds(const char *who, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_pos /* < 0: any */)
+{
+    if (n_scaffolds <= 0 || !scaffold_bounds || scaffold_bounds[0] != 0 || (n_pos >= 0 && scaffold_bounds[n_scaffolds] != n_pos)) {
+        isx_set_error(std::string(who) + ": scaffold_bounds must span [0, n_pos]");
+        return ISX_ERR_ARG;
+    }
+    for (int i = 0; i < n_scaffolds; i++)
+        if (scaffold_bounds[i + 1] <= scaffold_bounds[i]) { isx_set_error("scaffold_bounds must be strictly ascending"); return ISX_ERR_ARG; }
+    if (scaffold_bounds[n_scaffolds] > (int64_t)0xFFFFFFFFll) { isx_set_error(std::string(who) + ": flat space beyond 2^32 positions"); return ISX_ERR_ARG; }
+    return ISX_OK;
+}
+
+int isx_batch_genome_coverage(isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *scaffold_genome,
+                              int32_t n_genomes, int32_t mask_edges, int32_t hist_bins, isx_genome_cov *acc, uint32_t *hist,
+                              float *device_ms)
+{
+    NEED_RUN(b, acc);
+    int rc = check_scaffold_bounds("isx_batch_genome_coverage", n_scaffolds, scaffold_bounds, b->n_pos);
+    if (rc) return rc;
+    if (!hist || !scaffold_genome || n_genomes <= 0 || mask_edges < 0 || hist_bins < 2) {
+        isx_set_error("isx_batch_genome_coverage: n_genomes > 0, mask_edges >= 0, hist_bins >= 2");
+        return ISX_ERR_ARG;
+    }
+    for (int i = 0; i < n_scaffolds; i++)
+        if (scaffold_genome[i] < -1 || scaffold_genome[i] >= n_genomes) {
+            isx_set_error("isx_batch_genome_coverage: genome of scaffold " + std::to_string(i) + " outside [-1, n_genomes)");
+            return ISX_ERR_ARG;
+        }
+    if (b->lean && !b->d_counts && !b->d_entries) { isx_set_error("this batch lives in a lean pipe slot (isx_pipe_params.lean_output): its dense coverage / clonality arrays were not written"); return ISX_ERR_STATE; }
+    SummaryIn in{};
+    fill_summary_in(b, n_scaffolds, scaffold_bounds, in);
+    return run_genome_cov(in, b->S, scaffold_genome, n_genomes, mask_edges, hist_bins, acc, hist, device_ms);
+}
+
+int isx_snv_level_counts(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_snv, const isx_snv *snv,
+                         int32_t n_levels, isx_snv_level *out, float *device_ms)
+{
+    if (!ctx || !out || n_snv < 0 || (n_snv && !snv) || n_levels <= 0 || n_snv > 0x7FFFFFFFll) {
+        isx_set_error("isx_snv_level_counts: bad argument");
+        return ISX_ERR_ARG;
+    }
+    int rc = check_scaffold_bounds("isx_snv_level_counts", n_scaffolds, scaffold_bounds, -1);
+    if (rc) return rc;
+    return run_snv_levels(ctx->device, ctx->stream, n_scaffolds, scaffold_bounds, n_snv, snv, n_levels, out, device_ms);
+}
+
+int isx_ld_level_sums(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_ld, const isx_ld *ld,
+                      int32_t n_levels, isx_ld_level *out, float *device_ms)
+{
+    if (!ctx || !out || n_ld < 0 || (n_ld && !ld) || n_levels <= 0) {
+        isx_set_error("isx_ld_level_sums: bad argument");
+        return ISX_ERR_ARG;
+    }
+    int rc = check_scaffold_bounds("isx_ld_level_sums", n_scaffolds, scaffold_bounds, -1);
+    if (rc) return rc;
+    return run_ld_levels(ctx->device, ctx->stream, n_scaffolds, scaffold_bounds, n_ld, ld, n_levels, out, device_ms);
+}
+
 int isx_compare_coverage(isx_batch *a, isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, int32_t min_cov,
                          isx_compare_level *out, float *device_ms)
 {

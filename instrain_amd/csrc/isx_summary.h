@@ -122,3 +122,15 @@ int run_gene_cov(const SummaryIn &in, SummaryBuffers &B, const std::vector<GeneW
 int run_gene_snvs(isx_genes *g, int32_t n_scaffolds, const int64_t *bounds, const std::vector<GeneWork> &work, int64_t n_snv,
                   const isx_snv *snv, int32_t n_levels, isx_gene_mutation *mut_out, isx_gene_snv_count *cnt_out, float *ms);
 int run_gene_sites(isx_genes *g, double *sites, float *ms);
+
+// ---- genome_info roll-ups (isx_genomes.hip; genomeUtilities.py:145-269) ----
+// one level of the masked coverage distribution: acc / hist point at that level of genome 0, consecutive genomes lie acc_stride rows /
+// hist_stride words apart (both zeroed by the caller)
+void launch_genome_hist(hipStream_t s, const uint32_t *cov, uint32_t n_pos, const int64_t *sbounds, const int32_t *sgen, int n_scaf,
+                        int mask_edges, int hist_bins, isx_genome_cov *acc, size_t acc_stride, uint32_t *hist, size_t hist_stride);
+int run_genome_cov(const SummaryIn &in, SummaryBuffers &B, const int32_t *scaffold_genome, int n_genomes, int mask_edges, int hist_bins,
+                   isx_genome_cov *acc_out, uint32_t *hist_out, float *ms);
+int run_snv_levels(int device, hipStream_t s, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_snv, const isx_snv *snv,
+                   int32_t n_levels, isx_snv_level *out, float *device_ms);
+int run_ld_levels(int device, hipStream_t s, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_ld, const isx_ld *ld,
+                  int32_t n_levels, isx_ld_level *out, float *device_ms);

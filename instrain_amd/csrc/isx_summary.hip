@@ -822,6 +822,63 @@ int run_gene_cov(const SummaryIn &in, SummaryBuffers &B, const std::vector<GeneW
     return done(ISX_OK);
 }
 
+// ---- genome_info, coverage half (genomeUtilities.py:297-365): the levels are materialised as above, then one histogram pass per level
+// (isx_genomes.hip k_genome_hist).  Genomes are any subsets of the scaffolds; everything written is a sum, so batches add up ----
+int run_genome_cov(const SummaryIn &in, SummaryBuffers &B, const int32_t *scaffold_genome, int n_genomes, int mask_edges, int hist_bins,
+                   isx_genome_cov *acc_out, uint32_t *hist_out, float *ms)
+{
+    hipStream_t s = in.stream;
+    const uint32_t n_pos = in.n_pos;
+    const int n_scaf = in.n_scaffolds, M = in.M;
+    const size_t n_acc = (size_t)n_genomes * M, n_hist = n_acc * (size_t)hist_bins;
+    int rc;
+    B.fit_positions(n_pos);
+    if ((rc = dev_alloc(&B.cov, B.cap_pos)) || (rc = dev_alloc(&B.cv, B.cap_pos)) || (rc = dev_alloc(&B.cr, B.cap_pos))) return rc;
+    int64_t *d_sb = nullptr;
+    int32_t *d_sg = nullptr;
+    Acc *d_sacc = nullptr;
+    isx_genome_cov *d_acc = nullptr;
+    uint32_t *d_hist = nullptr;
+    auto done = [&](int code) {
+        void *ps[] = {d_sb, d_sg, d_sacc, d_acc, d_hist};
+        for (void *p : ps) if (p) isx_dev_free(p);
+        return code;
+    };
+#define GH_TRY(expr) do { if ((expr) != hipSuccess) { isx_set_error(std::string("HIP error in the genome coverage pass: ") + #expr); return done(ISX_ERR_HIP); } } while (0)
+    GH_TRY(isx_raw_dev_malloc(&d_sb, ((size_t)n_scaf + 1) * sizeof(int64_t)));
+    GH_TRY(isx_raw_dev_malloc(&d_sg, (size_t)n_scaf * sizeof(int32_t)));
+    GH_TRY(isx_raw_dev_malloc(&d_sacc, (size_t)n_scaf * sizeof(Acc)));
+    GH_TRY(isx_raw_dev_malloc(&d_acc, n_acc * sizeof(isx_genome_cov)));
+    GH_TRY(isx_raw_dev_malloc(&d_hist, n_hist * sizeof(uint32_t)));
+    GH_TRY(hipMemcpyAsync(d_sb, in.scaffold_bounds, ((size_t)n_scaf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    GH_TRY(hipMemcpyAsync(d_sg, scaffold_genome, (size_t)n_scaf * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    GH_TRY(hipMemsetAsync(d_sacc, 0, (size_t)n_scaf * sizeof(Acc), s));
+    GH_TRY(hipEventRecord(in.ev[0], s));
+    GH_TRY(hipMemsetAsync(d_acc, 0, n_acc * sizeof(isx_genome_cov), s));
+    GH_TRY(hipMemsetAsync(d_hist, 0, n_hist * sizeof(uint32_t), s));
+    const dim3 blk(256), gpos((n_pos + 255) / 256);
+    if (M > 1) {
+        GH_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
+        GH_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cv), 0x7FC00000, n_pos, s));
+        GH_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cr), 0x7FC00000, n_pos, s));
+    }
+    for (int mm = 0; mm < M; mm++) {
+        if (M == 1) launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
+        else hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
+                                (uint32_t)mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
+        launch_genome_hist(s, B.cov, n_pos, d_sb, d_sg, n_scaf, mask_edges, hist_bins, d_acc + mm, (size_t)M,
+                           d_hist + (size_t)mm * hist_bins, (size_t)M * hist_bins);
+    }
+    GH_TRY(hipGetLastError());
+    GH_TRY(hipEventRecord(in.ev[1], s));
+    GH_TRY(hipMemcpyAsync(acc_out, d_acc, n_acc * sizeof(isx_genome_cov), hipMemcpyDeviceToHost, s));
+    GH_TRY(hipMemcpyAsync(hist_out, d_hist, n_hist * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GH_TRY(isx_wait_stream(s));
+#undef GH_TRY
+    if (ms) { float v = 0.f; (void)hipEventElapsedTime(&v, in.ev[0], in.ev[1]); *ms = v; }
+    return done(ISX_OK);
+}
+
 void CompareBuffers::release()
 {
     void *ps[] = {cov_a, cov_b, scratch_f, bounds, acc_a, acc_b, both, rows, keys, idx, cand, snp_rows, cursors, temp};

@@ -349,6 +349,38 @@ class Batch:
                                                    out.ctypes.data, C.byref(ms)))
         return out, ms.value
 
+    def genome_coverage_raw(self, scaffold_bounds, scaffold_genome, n_genomes, mask_edges=100, hist_bins=4096):
+        """one isx_batch_genome_coverage call -> (GENOME_COV_DT [n_genomes, n_mm_bins], uint32 hist [n_genomes, n_mm_bins,
+        hist_bins], device ms); the last bin catches every coverage >= hist_bins - 1"""
+        sb = np.ascontiguousarray(scaffold_bounds, dtype=np.int64)
+        sg = np.ascontiguousarray(scaffold_genome, dtype=np.int32)
+        if len(sg) != len(sb) - 1:
+            raise IsxError(-1, "genome_coverage: one genome id per scaffold")
+        acc = np.zeros((max(int(n_genomes), 1), self.n_mm_bins), dtype=_lib.GENOME_COV_DT)
+        hist = np.zeros((max(int(n_genomes), 1), self.n_mm_bins, max(int(hist_bins), 1)), dtype=np.uint32)
+        ms = C.c_float(0)
+        check(self.lib.isx_batch_genome_coverage(self.h, len(sb) - 1, sb.ctypes.data, sg.ctypes.data, int(n_genomes), int(mask_edges),
+                                                 int(hist_bins), acc.ctypes.data, hist.ctypes.data, C.byref(ms)))
+        return acc, hist, ms.value
+
+    MAX_HIST_BINS = 1 << 22
+
+    def genome_coverage(self, scaffold_bounds, scaffold_genome, n_genomes, mask_edges=100, hist_bins=4096):
+        """masked coverage distribution of every genome (genomeUtilities.genomeLevel_coverage_info without iRep), mergeable:
+        scaffold_genome[s] = genome 0..n_genomes-1 of scaffold s in any order, -1 = in no genome -> (acc, hist, device ms) as
+        genome_coverage_raw, with a histogram that is always exact: when a counted coverage reaches hist_bins the pass runs again
+        with the next power of two above the largest one (refused beyond 2**22 bins)."""
+        acc, hist, ms = self.genome_coverage_raw(scaffold_bounds, scaffold_genome, n_genomes, mask_edges, hist_bins)
+        top = int(acc["max_cov"].max()) if acc.size else 0
+        if top >= int(hist_bins):
+            bins = 1 << top.bit_length()            # the next power of two above top
+            if bins > self.MAX_HIST_BINS:
+                raise IsxError(-3, "genome_coverage: a counted position has coverage %d; an exact histogram would need %d bins, "
+                                   "more than the %d this call goes up to" % (top, bins, self.MAX_HIST_BINS))
+            acc, hist, ms2 = self.genome_coverage_raw(scaffold_bounds, scaffold_genome, n_genomes, mask_edges, bins)
+            ms += ms2
+        return acc, hist, ms
+
     def profile_genes(self, genes, scaffold_bounds, gene_first, gene_last):
         """coverage half of the gene pass (isx_batch_profile_genes): genes [gene_first[s], gene_last[s]) of the Genes set lie on
         scaffold s of this batch -> (GENE_COV_DT rows [n_call_genes, n_mm_bins] in call order, scaffold flags [n_scaffolds,
@@ -374,6 +406,30 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def snv_level_counts(ctx, rows, scaffold_bounds, n_levels):
+    """calc_snps of every (scaffold, level) at once (isx_snv_level_counts) on SNV_DT rows in (gpos, mm) order
+    -> (SNV_LEVEL_DT [n_scaffolds, n_levels], device ms)"""
+    sb = np.ascontiguousarray(scaffold_bounds, dtype=np.int64)
+    rows = np.ascontiguousarray(rows, dtype=SNV_DT)
+    out = np.zeros((len(sb) - 1, int(n_levels)), dtype=_lib.SNV_LEVEL_DT)
+    ms = C.c_float(0)
+    check(ctx.lib.isx_snv_level_counts(ctx.h, len(sb) - 1, sb.ctypes.data, len(rows), rows.ctypes.data if len(rows) else None,
+                                       int(n_levels), out.ctypes.data, C.byref(ms)))
+    return out, ms.value
+
+
+def ld_level_sums(ctx, rows, scaffold_bounds, n_levels):
+    """the sums behind genomeUtilities._genome_wide_linkage of every (scaffold, level) (isx_ld_level_sums) on LD_DT rows in
+    (gpos_a, gpos_b, mm) order -> (LD_LEVEL_DT [n_scaffolds, n_levels], device ms)"""
+    sb = np.ascontiguousarray(scaffold_bounds, dtype=np.int64)
+    rows = np.ascontiguousarray(rows, dtype=LD_DT)
+    out = np.zeros((len(sb) - 1, int(n_levels)), dtype=_lib.LD_LEVEL_DT)
+    ms = C.c_float(0)
+    check(ctx.lib.isx_ld_level_sums(ctx.h, len(sb) - 1, sb.ctypes.data, len(rows), rows.ctypes.data if len(rows) else None,
+                                    int(n_levels), out.ctypes.data, C.byref(ms)))
+    return out, ms.value
 
 
 class Genes:

@@ -23,7 +23,7 @@ import pandas as pd
 
 from .. import dist as idist
 from .. import _lib, engine
-from . import gene_profile
+from . import gene_profile, genome_utilities
 from .snv_utilities import CLASSES, null_model_lut
 
 BASES = np.array(["A", "C", "T", "G", "N"])
@@ -521,12 +521,13 @@ def make_coverage_table_host(covT, clonT, clonTR, lengt, scaff, SNPTable):
     return pd.DataFrame(table, columns=COVERAGE_COLUMNS)
 
 
-def make_coverage_table(levels, lengt, scaff, SNPTable):
+def make_coverage_table(levels, lengt, scaff, SNPTable, snv_counts=None):
     """Mirror of make_coverage_table (profile_utilities.py:425-506): `levels` = this scaffold's row of
-    Batch.summarize() (device aggregates per mm); the SNV-table columns are computed here."""
+    Batch.summarize() (device aggregates per mm); the SNV-table columns are computed here from SNPTable -- or taken from
+    snv_counts, the scaffold's row of engine.snv_level_counts (one SNV_LEVEL_DT record per level of `levels`)."""
     table = {k: [] for k in COVERAGE_COLUMNS}
     n = float(lengt)
-    for r in levels:
+    for j, r in enumerate(levels):
         if not r['present']:
             continue                                    # not a key of covT for this scaffold
         mm = int(r['mm'])
@@ -534,7 +535,10 @@ def make_coverage_table(levels, lengt, scaff, SNPTable):
         mean = s1 / n
         var = max(s2 / n - mean * mean, 0.0)
         counted, rare = int(r['counted']), int(r['counted_rarefied'])
-        SNS_count, SNV_count, div_site_count, con_snps, pop_snps = calc_snps(SNPTable, mm)
+        if snv_counts is None:
+            SNS_count, SNV_count, div_site_count, con_snps, pop_snps = calc_snps(SNPTable, mm)
+        else:
+            SNS_count, SNV_count, div_site_count, con_snps, pop_snps = (int(snv_counts[j][f]) for f in ('sns', 'snv', 'divergent', 'con', 'pop'))
         table['scaffold'].append(scaff)
         table['length'].append(lengt)
         table['breadth'].append(int(r['nonzero']) / lengt)
@@ -894,11 +898,12 @@ class _BatchRun:
     released on the pipe that issued it -- the pipe is only replaced while nothing is in flight."""
 
     def __init__(self, bf, plan, refs, opt, make_pipe, depth, codes_of, est_segs, out, stage, bam=None, mm_values=None, mm_clamped=None,
-                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None):
+                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None, genomes=None):
         self.bf, self.plan, self.refs, self.opt, self.make_pipe, self.depth = bf, plan, refs, opt, make_pipe, depth
         self.codes_of, self.est_segs, self.out, self.stage, self.bam = codes_of, est_segs, out, stage, bam
         self.mm_values, self.mm_clamped, self.gset, self.logs = mm_values, mm_clamped, gset, logs
         self.scaffold_tables, self.scaffold_levels = scaffold_tables, scaffold_levels
+        self.genomes = genomes                       # genome_utilities.GenomeTables (profile_bam(stb=...)) or None
         self.ekw = dict(opt.filter, skip_mm=opt.skip_mm, window_length=opt.window_length)
         self.pipe = self.cap = None
         self.in_flight = []                          # submitted, not yet collected (at most `depth`)
@@ -961,7 +966,7 @@ class _BatchRun:
                 res["pair_names"] = g.pair_names
             splits = tables_to_splits(res, g.bounds, g.s_scaff, g.s_num, g.s_off, g.s_len, opt.min_freq, self.bam,
                                       min_cov=opt.min_cov, started=g.t_submit, mm_clamped=self.mm_clamped, mm_values=self.mm_values)
-            summaries = self.scaffold_tables is not None or self.scaffold_levels is not None
+            summaries = self.scaffold_tables is not None or self.scaffold_levels is not None or self.genomes is not None
             genes = self.gset is not None and bool(splits)
             if summaries or genes:
                 sb = np.r_[0, np.cumsum([self.refs[tid][1] for tid in g.tids])]
@@ -981,13 +986,34 @@ class _BatchRun:
             for lv in levels:
                 lv['mm'] = self.mm_values[lv['mm'].astype(np.int64)]
         tables = splits[0]._src[0] if splits else None
+        snv_levels = None
+        if self.genomes is not None:                # the batch's share of genome_info: everything below only ever adds
+            snv_levels = self.roll_up_genomes(g, slot, tables, sb, levels)
         for j, k in enumerate(g.items):
             tid, name, _ = self.plan[k]
             if self.scaffold_levels is not None:    # the device's per-(scaffold, mm) aggregates as they are
                 self.scaffold_levels[name] = levels[j][levels[j]['present'] != 0].copy()
             if self.scaffold_tables is not None:
-                snp = tables.snp_table(g.first_split[j], g.first_split[j + 1])     # the scaffold's rows in one cut
-                self.scaffold_tables[name] = make_coverage_table(levels[j], self.refs[tid][1], name, snp)
+                # the scaffold's rows in one cut -- not needed when the device counted them (calc_snps would be one lexsort per level)
+                snp = tables.snp_table(g.first_split[j], g.first_split[j + 1]) if snv_levels is None else None
+                self.scaffold_tables[name] = make_coverage_table(levels[j], self.refs[tid][1], name, snp,
+                                                                 None if snv_levels is None else snv_levels[j])
+
+    def roll_up_genomes(self, g, slot, tables, sb, levels):
+        """SNV counts and linkage sums per (scaffold, level) and the genomes' coverage distribution of this batch, added to the
+        run's GenomeTables -> the SNV counts [n_scaffolds, n_levels]"""
+        names = [self.plan[k][1] for k in g.items]
+        n_levels = slot.n_mm_bins
+        empty = tables is None
+        snv_levels, _ = engine.snv_level_counts(slot.ctx, np.zeros(0, _lib.SNV_DT) if empty else tables.snv, sb, n_levels)
+        ld_levels, _ = engine.ld_level_sums(slot.ctx, np.zeros(0, _lib.LD_DT) if empty else tables.ld, sb, n_levels)
+        ids, local = self.genomes.batch_genomes(names)
+        acc = hist = None
+        if local:
+            acc, hist, _ = slot.genome_coverage(sb, ids, len(local), mask_edges=self.genomes.mask_edges)
+        self.genomes.add_batch(names, [self.refs[tid][1] for tid in g.tids], levels, snv_levels, ld_levels, local, acc, hist,
+                               mms=self.mm_values)
+        return snv_levels
 
     def profile_genes(self, g, slot, splits, sb):
         """profile_genes_from_profile of every scaffold of the batch (gene_profile.py)"""
@@ -1084,6 +1110,9 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     cumulative_scaffold_table from the device summaries), `logs` (list that receives the failure lines),
     `gene_file` (prodigal .fna) or `genes` ((scaff2geneinfo, scaff2gene2sequence)) with `gene_tables` (dict that receives genes_table,
     genes_coverage, genes_clonality, genes_SNP_count and SNP_mutation_types: the gene pass, gene_profile.py, on every batch),
+    `stb` (scaffold -> genome, a dict or the path of a two-column tab-separated file) with `genome_tables` (dict that receives
+    genome_info, scaffold2bin and bin2length: genomeUtilities.genomeLevel_from_IS from per-batch device roll-ups,
+    genome_utilities.GenomeTables; scaffolds the stb does not name are left out, a genome may span batches; without `stb` no such call is made),
     `batch_positions` / `batch_reads` (size of a device batch; `batch_observations` is accepted as 150 x batch_reads), `pipe_depth` (device batches in flight: the front end
     prepares batch k + 1 while batch k is profiled and its tables are cut), `stats` (dict that receives stage times).
     The BAM's reads go to the device as read segments (isx_pipe_submit_bam on a read-level pipe): the host never expands a
@@ -1134,9 +1163,12 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
         est_segs = estimate_segments(bf.info, reads_per_ref, plan)
         item_groups = idist.pack_batches([refs[tid][1] for tid, _, _ in plan], est_segs, opt.batch_positions, opt.batch_segs)
         depth = pipe_depth_of(opt, len(item_groups))
+        genomes = None
+        if kwargs.get('stb') is not None:
+            genomes = genome_utilities.GenomeTables(kwargs['stb'], {name: len(seq) for name, seq in s2s.items()})      # scaffold2length
         run = _BatchRun(bf, plan, refs, opt, functools.partial(open_pipe, ctx, opt, n_mm, depth), depth, codes_of, est_segs, out, stage,
                         bam=bam, mm_values=mm_values, mm_clamped=mm_clamped, gset=gset, logs=logs,
-                        scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'))
+                        scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'), genomes=genomes)
         # the pipe (pinned staging, device arena: tens of ms) is set up by one helper thread while another lays the groups out
         # (sequence codes, split tables: Python + numpy) -- a group's layout is then ready when the group before it is being handed
         # over (isx_pipe_submit_bam runs without the GIL)
@@ -1145,6 +1177,10 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
         pipe_f.result()
         stage("setup_ms")
         run.run(item_groups, layouts)
+        if genomes is not None and kwargs.get('genome_tables') is not None:
+            gt = kwargs['genome_tables']
+            gt['scaffold2bin'], gt['bin2length'] = genomes.stb, genomes.bin2length
+            gt['genome_info'] = genomes.genome_info(skip_mm_profiling=opt.skip_mm)
         if gset is not None:
             gene_profile.finish_genes(gset, kwargs['gene_tables'] if kwargs.get('gene_tables') is not None else {})
         return out
