@@ -65,6 +65,16 @@ def scaffold_half(gdb, stb, b2l):
     return pd.DataFrame(rows)
 
 
+def calc_snps(sdb, mm):
+    """the reference's calc_snps (profile/snv_utilities.py:249-272) on one scaffold's SNV table (columns position, mm, allele_count,
+    class): of the rows at levels <= mm every position keeps its highest one -> (SNS, SNV, divergent, consensus, population)"""
+    if len(sdb) == 0:
+        return 0, 0, 0, 0, 0
+    db = sdb[sdb['mm'] <= mm].sort_values('mm').drop_duplicates(subset=['position'], keep='last')
+    return (len(db[db['allele_count'] == 1]), len(db[db['allele_count'] > 1]), len(db),
+            len(db[db['class'].isin(['SNS', 'con_SNV', 'pop_SNV'])]), len(db[db['class'].isin(['SNS', 'pop_SNV'])]))
+
+
 def coverage_half(covT, stb, s2l, relevant, mms, mask_edges=100):
     rows = []
     genome2scaffolds = {}
@@ -217,6 +227,27 @@ def coverage_rows(covT, s2l, names, scaffold_genome, n_genomes, levels, mask_edg
     hist = np.zeros((n_genomes, len(levels), bins), dtype=np.uint32)
     for gi, row in enumerate(covs):
         for j, c in enumerate(row):
+            acc[gi, j] = (len(c), int(c.sum()), int((c * c).sum()), int(c.max()) if len(c) else 0, 0)
+            hist[gi, j] = np.bincount(np.minimum(c, bins - 1), minlength=bins)
+    return acc, hist
+
+
+def coverage_rows_flat(cov_levels, bounds, scaffold_genome, n_genomes, mask_edges=100, hist_bins=None):
+    """coverage_rows on arrays: cov_levels [n_levels, n_pos] = the cumulative coverage of every flat position at every level, bounds =
+    the scaffold bounds of the flat space, scaffold_genome[s] = genome id or -1 -> (GENOME_COV_DT [n_genomes, n_levels], hist
+    [n_genomes, n_levels, bins]); the last bin catches every coverage >= bins - 1"""
+    cov_levels = np.asarray(cov_levels, dtype=np.int64)
+    keep = np.full(cov_levels.shape[1], -1, dtype=np.int64)           # the genome a position counts for
+    for s, g in enumerate(scaffold_genome):
+        lo, hi = int(bounds[s]) + mask_edges, int(bounds[s + 1]) - mask_edges
+        if g >= 0 and hi > lo:                                          # shorter than twice the mask, or exactly that: nothing counts
+            keep[lo:hi] = g
+    bins = hist_bins or max(int(cov_levels[:, keep >= 0].max(initial=0)) + 1, 2)
+    acc = np.zeros((n_genomes, cov_levels.shape[0]), dtype=_lib.GENOME_COV_DT)
+    hist = np.zeros((n_genomes, cov_levels.shape[0], bins), dtype=np.uint32)
+    for gi in range(n_genomes):
+        for j in range(cov_levels.shape[0]):
+            c = cov_levels[j, keep == gi]
             acc[gi, j] = (len(c), int(c.sum()), int((c * c).sum()), int(c.max()) if len(c) else 0, 0)
             hist[gi, j] = np.bincount(np.minimum(c, bins - 1), minlength=bins)
     return acc, hist

@@ -104,3 +104,36 @@ def test_genome_struct_sizes_match_header(tmp_path):
     c_sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
     assert c_sizes == [_lib.GENOME_COV_DT.itemsize, _lib.SNV_LEVEL_DT.itemsize, _lib.LD_LEVEL_DT.itemsize], c_sizes
     assert all(s in _lib.SYMBOLS for s in ("isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums"))
+
+
+@pytest.mark.parametrize("name", ["single", "double", "triple"])
+def test_calc_snps_restatement_vs_reference_tables(name):
+    """tests/genome_ref.py calc_snps (what the GPU tests compare isx_snv_level_counts with) against the five counts the reference's own
+    make_coverage_table -> calc_snps wrote into the stored cumulative scaffold tables of the merge goldens, from the stored SNV tables
+    they were made of (tests/golden/make_merge_golden.py): every level, the gap between levels 2 and 7 included.  (The divergent /
+    sns / snv / con / pop integers of genome_info_inputs.npz are random draws of make_genome_info_golden.py, not counts of any SNV
+    table -- on gA_1 `divergent` falls from 6 to 2 between levels 0 and 1, which no table gives -- so they cannot pin this rule.)"""
+    snv = pd.read_csv(os.path.join(GOLDEN, "merge_%s_cumulative_snv_table.csv" % name))
+    sdb = pd.read_csv(os.path.join(GOLDEN, "merge_%s_cumulative_scaffold_table.csv" % name))
+    assert len(sdb) >= 3 and snv.duplicated("position").any()                  # positions with rows at several levels
+    for _, r in sdb.iterrows():
+        exp = tuple(int(r[c]) for c in ("SNS_count", "SNV_count", "divergent_site_count", "consensus_divergent_sites", "population_divergent_sites"))
+        assert genome_ref.calc_snps(snv, int(r["mm"])) == exp, (name, int(r["mm"]))
+    assert genome_ref.calc_snps(snv[:0], 3) == (0, 0, 0, 0, 0)
+
+
+def test_coverage_rows_flat_equals_coverage_rows(inp):
+    """the array form of the coverage reference == the covT form on the golden's inputs (mask 100 and 0, a short catch-all histogram)"""
+    names, levels = inp["names"], inp["levels"]
+    ids, genomes = gu.GenomeTables(inp["stb"], inp["s2l"]).batch_genomes(names)
+    bounds = np.r_[0, np.cumsum(inp["lengths"])]
+    cov = np.zeros((len(levels), int(bounds[-1])), dtype=np.int64)
+    for i, n in enumerate(names):
+        for m, ser in inp["covT"][n].items():
+            for j, lv in enumerate(levels):
+                if m <= lv:
+                    np.add.at(cov[j], bounds[i] + np.asarray(ser.index), np.asarray(ser.values))
+    for mask, bins in ((100, None), (0, None), (100, 8)):
+        a, h = genome_ref.coverage_rows(inp["covT"], inp["s2l"], names, ids, len(genomes), levels, mask_edges=mask, hist_bins=bins)
+        a2, h2 = genome_ref.coverage_rows_flat(cov, bounds, ids, len(genomes), mask_edges=mask, hist_bins=bins)
+        assert a.tobytes() == a2.tobytes() and h.shape == h2.shape and (h == h2).all(), (mask, bins)
