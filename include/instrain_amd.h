@@ -378,6 +378,67 @@ int isx_compare_scaffolds(isx_batch *a, isx_batch *b, int32_t n_scaffolds, const
                           double min_freq, isx_compare_level *out, int64_t *n_snp_rows, float *device_ms);
 int isx_compare_fetch_snps(isx_batch *a, isx_compare_snp *out);
 
+/* ---- compare, a whole sample set (readComparer.py:35-143 compare_scaffold over every pair of a scaffold's profiles,
+ *      compare_controller.py:611-658 the loop over scaffolds; compare_utils.py:86-107 SC_object_wrapper) ----
+ * A comparison set keeps of every sample only what the pair loop reads: per level one bit per position ("coverage cumulated over
+ * levels <= mm reaches min_cov"), per (scaffold, level) the covT-key flag, and the highest-mm SNV row of every position.  Batches are
+ * added one by one and may be destroyed / released right after; isx_cmpset_compare then counts every pair in one pass.
+ *
+ * The set owns its position space: the caller's scaffolds in the caller's order, each starting on a 64-position word boundary
+ * (pad bits are zero), so no 64-bit word belongs to two scaffolds.  The three helpers below are plain host code (no device). */
+typedef struct isx_cmpset isx_cmpset;
+#define ISX_CMPSET_MAX_LEVELS 128       /* axis levels (sorted union of the samples' real mm values) one set compares: more is ISX_ERR_CAPACITY */
+#define ISX_CMPSET_MAX_SAMPLES 4096
+
+/* word_offsets[n_scaffolds + 1]: first word of every scaffold, then the total; scaffold i's set positions are
+ * [64 * word_offsets[i], 64 * word_offsets[i] + length_i).  Lengths > 0, 64 * total < 2^32.  With isx_cmpset_tiles this is the unit
+ * of work that compare_controller.py:611-658 makes one ScaffoldComparison object per scaffold for. */
+int isx_cmpset_layout(int32_t n_scaffolds, const int64_t *scaffold_lengths, int64_t *word_offsets);
+
+/* the pair kernel's tile directory: every scaffold cut into runs of at most tile_words words; a tile never crosses a scaffold */
+typedef struct {
+    int64_t word0;              /* first word (set space) */
+    int32_t n_words, scaffold;
+} isx_cmpset_tile;
+/* -> number of tiles (< 0: an ISX_ERR_* code); tiles == NULL counts only */
+int64_t isx_cmpset_tiles(int32_t n_scaffolds, const int64_t *scaffold_lengths, int32_t tile_words, isx_cmpset_tile *tiles);
+
+/* The level axis (readComparer.py:162-169: the union of the covT keys, coverage carried from key to key): sample s has n_levels[s] levels whose real mm values (strictly ascending, 0..65535) follow each other in level_mm.
+ * axis[cap_axis] receives the sorted union, *n_axis its size (ISX_ERR_CAPACITY beyond cap_axis); map[s * cap_axis + a] = the sample's
+ * own highest level with value <= axis[a] (a level beyond its last carries over, the `mm >= M` rule of isx_compare_scaffolds), -1 = none yet. */
+int isx_cmpset_level_map(int32_t n_samples, const int32_t *n_levels, const int32_t *level_mm, int32_t cap_axis, int32_t *axis,
+                         int32_t *n_axis, int32_t *map);
+
+/* the profiles of one comparison (compare_controller.py:611-658 / readComparer.py:35-59: names, covTs, SNPtables) */
+int isx_cmpset_create(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_lengths, int32_t min_cov, isx_cmpset **out);
+void isx_cmpset_destroy(isx_cmpset *set);
+
+/* What `batch` (a completed batch of the set's ctx, pipe slots included; not a lean slot) holds of sample `sample` (0 ..
+ * ISX_CMPSET_MAX_SAMPLES - 1).  batch_scaffold_bounds[n_batch_scaffolds + 1] spans the batch's flat space as for isx_batch_summarize;
+ * set_scaffold_ids[i] = the set's scaffold that batch scaffold i is (same length), -1 = not in the set: skipped.  level_mm_values[n_mm_bins
+ * of the batch]: the real mm of every device level, strictly ascending (NULL: level k is mm k); every batch of one sample brings the same
+ * values.  A sample may arrive in several batches, in any scaffold order; the same (sample, scaffold) twice is ISX_ERR_STATE.  All
+ * arguments are checked on the host before anything is launched.  Replaces the per-profile part of compare_scaffold's inputs:
+ * readComparer.py:145-191 (covT cumulated and thresholded) and compare_utils.py:124-138 / readComparer.py:239-243 (the last SNP row). */
+int isx_cmpset_add(isx_cmpset *set, int32_t sample, isx_batch *batch, int32_t n_batch_scaffolds, const int64_t *batch_scaffold_bounds,
+                   const int32_t *set_scaffold_ids, const int32_t *level_mm_values);
+
+/* sizes of the next isx_cmpset_compare (readComparer.py:162 over all samples): samples (highest index added + 1), axis levels, their real mm values (axis_mm[ISX_CMPSET_MAX_LEVELS] or NULL) */
+int isx_cmpset_axis(isx_cmpset *set, int32_t *n_samples, int32_t *n_levels, int32_t *axis_mm);
+
+/* Every pair i < j (pair p enumerates (0,1), (0,2), ... as itertools.combinations) over every scaffold and axis level:
+ * out[pair][scaffold][axis level], cap_rows >= n_pairs * n_scaffolds * n_levels.  Fields as for isx_compare_scaffolds with mm the real
+ * value; a pair is compared on a scaffold only when BOTH samples have it (any level present there: ScaffoldComparison.add_profile over
+ * _get_covt_keys) -- otherwise its rows have present_a = present_b = 0.  -2 marks a failed (pair, scaffold).  Integer arithmetic and
+ * integer atomics only: two calls give identical bytes.  Replaces readComparer.py:80-121 for all pairs at once. */
+int isx_cmpset_compare(isx_cmpset *set, double min_freq, int64_t cap_rows, isx_compare_level *out, float *device_ms);
+
+/* The reference's Mdb rows (--store_mismatch_locations, readComparer.py:107-115) of ONE pair i < j, with the min_freq of the last isx_cmpset_compare (which must
+ * have run since the last add).  *n_rows = rows isx_cmpset_fetch_snps delivers, sorted by (mm, gpos); gpos is the SET position (host:
+ * scaffold = the one whose 64 * word_offsets contains it).  Rows of failed scaffolds are included: the caller drops them. */
+int isx_cmpset_pair_snps(isx_cmpset *set, int32_t i, int32_t j, int64_t *n_rows);
+int isx_cmpset_fetch_snps(isx_cmpset *set, isx_compare_snp *rows);
+
 /* ---- gene profiling (GeneProfile.py:304-707 profile_genes_from_profile: `inStrain profile -g genes.fna`) ----
  * A gene set lives on the device for as long as the caller keeps it: coordinates + the genes' own letters (upper-case
  * A/C/G/T/N as in the .fna, gene orientation), uploaded once.  Genes of one scaffold are consecutive in the set.

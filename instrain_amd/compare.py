@@ -10,8 +10,15 @@ position-sized work (cumulate covT over mm, threshold at min_cov, intersect / un
 comparison (highest-mm row per position, merge of the two samples' rows, consensus / population
 verdicts, masking with the covered-in-both set per mm) run on the device (isx_compare_coverage /
 isx_compare_scaffolds); the per-mm bookkeeping and the column naming here.
+
+A whole sample set (every pair of every scaffold, compare_controller.py:611-658): SampleSet keeps a small per-sample sketch on the
+device (isx_cmpset_*: one bit per position and level, the covT-key flags, the last SNV row of every position), so batches -- pipe
+slots included -- can go as soon as they have been added; compare() then counts all pairs in one pass.  genome_wide() is
+genomeUtilities._genome_wide_readComparer (genomeUtilities.py:739-800) after _add_stb (:430-448), on the host.
 """
 import ctypes as C
+import itertools
+import time
 
 import numpy as np
 
@@ -88,3 +95,186 @@ def compare_scaffolds(batch1, batch2, scaffold_bounds, scaffold_names=None, name
             raw, scaf = raw[ok], scaf[ok]
         mdb = {"raw": raw, "scaffold": scaf, "position": raw["gpos"].astype(np.int64) - sb[scaf]}
     return table, mdb, ms.value
+
+
+# ---- a whole sample set (isx_cmpset_*) ----
+def set_layout(scaffold_lengths):
+    """first 64-position word of every scaffold in a set's own position space, then the total (isx_cmpset_layout; host only)"""
+    ln = np.ascontiguousarray(scaffold_lengths, dtype=np.int64)
+    off = np.zeros(len(ln) + 1, dtype=np.int64)
+    check(_lib.load().isx_cmpset_layout(len(ln), ln.ctypes.data, off.ctypes.data))
+    return off
+
+
+def tile_directory(scaffold_lengths, tile_words):
+    """the pair kernel's tiles (word0, n_words, scaffold): runs of at most tile_words words that never cross a scaffold (host only)"""
+    lib = _lib.load()
+    ln = np.ascontiguousarray(scaffold_lengths, dtype=np.int64)
+    n = lib.isx_cmpset_tiles(len(ln), ln.ctypes.data, int(tile_words), None)
+    if n < 0:
+        check(int(n))
+    tiles = np.zeros(n, dtype=_lib.CMPSET_TILE_DT)
+    lib.isx_cmpset_tiles(len(ln), ln.ctypes.data, int(tile_words), tiles.ctypes.data)
+    return tiles
+
+
+def level_map(sample_mm_values, cap_axis=_lib.CMPSET_MAX_LEVELS):
+    """-> (axis: sorted union of the samples' real mm values, map[sample, axis level] = the sample's own highest level with a value
+    <= the axis level's, -1 = none yet) (isx_cmpset_level_map; host only)"""
+    n_levels = np.array([len(v) for v in sample_mm_values], dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.int32) for v in sample_mm_values] + [np.zeros(0, np.int32)]))
+    axis, n_axis = np.zeros(cap_axis, dtype=np.int32), C.c_int32(0)
+    lmap = np.zeros((len(n_levels), cap_axis), dtype=np.int32)
+    check(_lib.load().isx_cmpset_level_map(len(n_levels), n_levels.ctypes.data, flat.ctypes.data, int(cap_axis), axis.ctypes.data,
+                                           C.byref(n_axis), lmap.ctypes.data))
+    return axis[:n_axis.value].copy(), lmap[:, :n_axis.value].copy()
+
+
+class SampleSet:
+    """The samples of one `inStrain compare` run on the device.  scaffold_names / scaffold_lengths: the scaffolds to compare, in the
+    order of the output.  Samples are numbered in the order of their first add_batch."""
+
+    def __init__(self, ctx, scaffold_names, scaffold_lengths, min_cov=5):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.names = list(scaffold_names)
+        self.lengths = np.ascontiguousarray(scaffold_lengths, dtype=np.int64)
+        if len(self.names) != len(self.lengths) or len(set(self.names)) != len(self.names):
+            raise ValueError("SampleSet: one length per scaffold, every scaffold once")
+        self.index = {n: i for i, n in enumerate(self.names)}
+        self.offsets = set_layout(self.lengths) * 64            # first set position of every scaffold
+        self.samples = []
+        self.failed = set()                                     # scaffolds on which a pair of the last compare() failed
+        self.device_ms, self.levels = 0.0, None
+        h = C.c_void_p()
+        check(self.lib.isx_cmpset_create(ctx.h, len(self.names), self.lengths.ctypes.data, int(min_cov), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def add_batch(self, sample_name, batch, batch_scaffold_names, batch_bounds, mm_values=None):
+        """what `batch` (a run Batch or a collected pipe slot) holds of the sample; scaffolds the set does not name are skipped.
+        mm_values: the real mm of every device level (profile_bam's mm_values), None = level k is mm k.  The batch may be closed /
+        its slot released as soon as this returns."""
+        bb = np.ascontiguousarray(batch_bounds, dtype=np.int64)
+        ids = np.array([self.index.get(n, -1) for n in batch_scaffold_names], dtype=np.int32)
+        if len(bb) != len(ids) + 1:
+            raise ValueError("add_batch: batch_bounds has one entry more than the batch has scaffolds")
+        mmv = None if mm_values is None else np.ascontiguousarray(mm_values, dtype=np.int32)
+        if mmv is not None and len(mmv) != batch.n_mm_bins:
+            raise ValueError("add_batch: one mm value per level of the batch")
+        known = sample_name in self.samples
+        check(self.lib.isx_cmpset_add(self.h, self.samples.index(sample_name) if known else len(self.samples), batch.h, len(ids),
+                                      bb.ctypes.data, ids.ctypes.data, None if mmv is None else mmv.ctypes.data))
+        if not known:                                           # (a refused batch leaves the set as it was)
+            self.samples.append(sample_name)
+
+    def compare(self, min_freq=0.05, logs=None):
+        """-> the comparisonsTable rows (the columns of compare_scaffolds) of every pair of samples over every scaffold both have,
+        ordered by (scaffold, pair as itertools.combinations, mm).  A scaffold on which ANY pair fails gives no row at all and one
+        failure line in `logs` (compare_utils.py:86-107: results = None for the whole scaffold)."""
+        n_s, n_a = C.c_int32(0), C.c_int32(0)
+        check(self.lib.isx_cmpset_axis(self.h, C.byref(n_s), C.byref(n_a), None))
+        pairs = list(itertools.combinations(range(n_s.value), 2))
+        out = np.zeros((len(pairs), len(self.names), n_a.value), dtype=_lib.COMPARE_LEVEL_DT)
+        ms = C.c_float(0)
+        check(self.lib.isx_cmpset_compare(self.h, float(min_freq), out.size, out.ctypes.data, C.byref(ms)))
+        self.device_ms = ms.value
+        self.levels = out                                       # the device's rows as they came: [pair, scaffold, axis level]
+        by_scaffold = out.transpose(1, 0, 2)
+        present = (by_scaffold["present_a"] != 0) | (by_scaffold["present_b"] != 0)
+        failed = (by_scaffold["consensus_snps"] == -2).any(axis=(1, 2)) if out.size else np.zeros(len(self.names), bool)
+        self.failed = set(np.flatnonzero(failed).tolist())
+        for sc in sorted(self.failed):
+            have = sorted({i for p in np.flatnonzero(present[sc].any(axis=1)) for i in pairs[p]})
+            line = "\n{1} DEBUG FAILURE CompareScaffold {0} {2}\n".format(self.names[sc], time.strftime('%m-%d %H:%M'),
+                                                                         str([self.samples[i] for i in have]))
+            if logs is not None:
+                logs.append(line)
+        present[failed] = False
+        table = []
+        for sc, p, a in np.argwhere(present):
+            r, mLen = by_scaffold[sc, p, a], int(self.lengths[sc])
+            bases = int(r["both"])
+            snps, popsnps = int(r["consensus_snps"]), int(r["population_snps"])
+            table.append({"mm": int(r["mm"]), "scaffold": self.names[sc], "name1": self.samples[pairs[p][0]],
+                          "name2": self.samples[pairs[p][1]],
+                          "coverage_overlap": r["both"] / r["either"] if r["either"] > 0 else 0,
+                          "compared_bases_count": bases, "percent_genome_compared": bases / mLen, "length": mLen,
+                          "consensus_SNPs": snps, "population_SNPs": popsnps,
+                          "conANI": (bases - snps) / bases if bases else np.nan,
+                          "popANI": (bases - popsnps) / bases if bases else np.nan})
+        return table
+
+    def mismatch_locations(self, name1, name2):
+        """the mismatch rows (--store_mismatch_locations) of one pair, as compare_scaffolds' Mdb: {'raw': COMPARE_SNP_DT rows sorted
+        by (mm, set position), 'scaffold': index in the set, 'position': on the scaffold}; name1 is the sample added first.  Needs a
+        compare() since the last add_batch; rows of its failed scaffolds are left out."""
+        i, j = self.samples.index(name1), self.samples.index(name2)
+        if i >= j:
+            raise ValueError("mismatch_locations: name1 must be the sample that was added before name2")
+        n = C.c_int64(0)
+        check(self.lib.isx_cmpset_pair_snps(self.h, i, j, C.byref(n)))
+        raw = np.zeros(n.value, dtype=_lib.COMPARE_SNP_DT)
+        if n.value:
+            check(self.lib.isx_cmpset_fetch_snps(self.h, raw.ctypes.data))
+        scaf = np.searchsorted(self.offsets, raw["gpos"].astype(np.int64), side="right") - 1
+        if self.failed:
+            ok = ~np.isin(scaf, sorted(self.failed))
+            raw, scaf = raw[ok], scaf[ok]
+        return {"raw": raw, "scaffold": scaf, "position": raw["gpos"].astype(np.int64) - self.offsets[scaf]}
+
+    def close(self):
+        if self.h:
+            self.lib.isx_cmpset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def genome_wide(table, stb, bin2length=None, mm_level=False):
+    """genomeUtilities._genome_wide_readComparer (genomeUtilities.py:739-800) on _add_stb(table, stb) (:430-448): the scaffold-level
+    comparison rows rolled up per (genome, name1, name2) -- per mm when mm_level, else from every scaffold's highest-mm row.
+    table: compare()'s rows (or a DataFrame of them); stb: scaffold -> genome; scaffolds it does not name are left out.
+    -> DataFrame with the reference's columns and row order, None when there is no row / no genome (as _add_stb)."""
+    import pandas as pd
+    gdb = table.copy() if isinstance(table, pd.DataFrame) else pd.DataFrame(list(table))
+    if len(gdb) == 0:
+        return None
+    gdb["genome"] = gdb["scaffold"].map(stb)
+    if gdb["genome"].notna().sum() == 0:
+        return None
+    key = ["scaffold", "name1", "name2"]
+    gdb = gdb.sort_values("mm", kind="stable")
+    if not mm_level:
+        gdb = gdb.drop_duplicates(subset=key, keep="last").copy()
+        gdb["mm"] = 0
+    n = gdb["compared_bases_count"].astype(np.float64)
+    gdb["_w_overlap"] = gdb["coverage_overlap"].astype(np.float64) * n
+    ani = [c for c in ("ANI", "popANI", "conANI") if c in gdb.columns]
+    for c in ani:                                   # a NaN ANI (nothing compared on the scaffold) counts as 0 (:788)
+        v = gdb[c].astype(np.float64)
+        gdb["_w_" + c] = np.where(v == v, v * n, 0.0)
+    sums = [c for c in ("compared_bases_count", "consensus_SNPs", "population_SNPs") if c in gdb.columns]
+    parts = []
+    for mm in sorted(gdb["mm"].unique()):
+        odb = gdb[gdb["mm"] <= mm].drop_duplicates(subset=key, keep="last")
+        g = odb.groupby(["genome", "name1", "name2"], sort=True)[sums + ["_w_overlap"] + ["_w_" + c for c in ani]].sum().reset_index()
+        tcb = g["compared_bases_count"]
+        some = (tcb != 0).to_numpy()
+        d = {"genome": g["genome"], "name1": g["name1"], "name2": g["name2"], "mm": mm}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d["coverage_overlap"] = np.where(some, g["_w_overlap"].to_numpy() / tcb.to_numpy(), np.nan)
+            for c in sums:
+                d[c] = g[c]
+            for c in ani:
+                d[c] = np.where(some, g["_w_" + c].to_numpy() / tcb.to_numpy(), np.nan)
+            if bin2length is not None:
+                d["percent_compared"] = tcb.to_numpy() / g["genome"].map(bin2length).to_numpy(dtype=np.float64)
+        parts.append(pd.DataFrame(d))
+    db = pd.concat(parts, ignore_index=True)
+    if not mm_level:
+        del db["mm"]
+    return db

@@ -1755,7 +1755,7 @@ int isx_batch_summarize_genomes(isx_batch *b, int32_t n_scaffolds, const int64_t
     return run_genome_summary(in, b->S, n_genomes, genome_first_scaffold, mask_edges, out, device_ms);
 }
 
-static void fill_summary_in(isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, SummaryIn &in)
+void fill_summary_in(isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, SummaryIn &in)
 {
     in.stream = b->ctx->stream; in.ev = b->ev_sum;
     in.n_pos = (uint32_t)b->n_pos; in.n_scaffolds = n_scaffolds; in.M = b->M; in.scaffold_bounds = scaffold_bounds;

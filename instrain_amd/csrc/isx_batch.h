@@ -179,4 +179,6 @@ int finish_pass_sizes(isx_batch *b, uint32_t *cap_flags, hipStream_t link_stream
 int finish_pass_link(isx_batch *b, hipStream_t link_stream = nullptr);
 // grow the tables named by cap_flags (x4 up to their hard bounds); the pass must then be repeated
 int batch_grow_tables(isx_batch *b, uint32_t cap_flags);
+// a completed batch as the summary / compare passes read it (isx_api.hip; also isx_compare_set.hip)
+void fill_summary_in(isx_batch *b, int32_t n_scaffolds, const int64_t *scaffold_bounds, SummaryIn &in);
 }

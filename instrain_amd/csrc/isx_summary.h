@@ -80,6 +80,13 @@ struct CompareSnpIn {                       // nullptr lut = coverage half only
 int run_compare(const SummaryIn &a, const SummaryIn &b, uint32_t min_cov, const CompareSnpIn &snp, CompareBuffers &B,
                 isx_compare_level *host_out, float *ms);
 
+// One level of what run_compare materialises, for the comparison set (isx_compare_set.hip): level `mm` of `in` applied onto cov[n_pos]
+// (zeroed by the caller before level 0; f0 / f1: 2 x n_pos floats of scratch), the level's Acc.present of every scaffold of
+// in.scaffold_bounds (on the device: d_bounds) into present_out[n_scaffolds].  acc_scratch: level_acc_bytes(n_scaffolds) device bytes.
+size_t level_acc_bytes(int n_seg);
+void launch_level_cumulate(const SummaryIn &in, int mm, uint32_t *cov, float *f0, float *f1, const int64_t *d_bounds, void *acc_scratch,
+                           uint32_t *present_out);
+
 // the mm path's entry table (window slabs + overflow) compacted and ordered by (gpos, mm) on the device, then brought to
 // host_out: by one hipMemcpyAsync, or by `copier` (device source, host destination, bytes, stream) when the caller has a
 // faster way to pageable memory (a pipe's pinned staging + its host threads)

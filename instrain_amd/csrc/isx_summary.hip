@@ -896,6 +896,38 @@ static int ensure(T **p, size_t have, size_t want)
     return ISX_OK;
 }
 
+// ---- one level of run_compare's materialisation for a caller outside this file (isx_compare_set.hip) ----
+namespace {
+__global__ void k_copy_present(const Acc *acc, int n_seg, uint32_t *out)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < n_seg) out[s] = acc[s].present;
+}
+}  // namespace
+
+size_t level_acc_bytes(int n_seg) { return (size_t)std::max(n_seg, 1) * sizeof(Acc); }
+
+void launch_level_cumulate(const SummaryIn &in, int mm, uint32_t *cov, float *f0, float *f1, const int64_t *d_bounds, void *acc_scratch,
+                           uint32_t *present_out)
+{
+    hipStream_t s = in.stream;
+    const uint32_t n_pos = in.n_pos;
+    const int n_seg = in.n_scaffolds;
+    Acc *acc = reinterpret_cast<Acc *>(acc_scratch);
+    const dim3 blk(256), gpos((n_pos + 255) / 256), gseg((n_seg + 255) / 256);
+    hipLaunchKernelGGL(k_reset_acc, gseg, blk, 0, s, acc, n_seg);
+    if (mm < in.M) {
+        if (in.M == 1) {
+            launch_level_dense(in, gpos, blk, s, n_pos, cov, f0, f1);
+            hipLaunchKernelGGL(k_present_dense, gpos, blk, 0, s, cov, n_pos, d_bounds, n_seg, acc);
+        } else {
+            hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
+                               (uint32_t)mm, cov, f0, f1, d_bounds, n_seg, acc);
+        }
+    }
+    hipLaunchKernelGGL(k_copy_present, gseg, blk, 0, s, acc, n_seg, present_out);
+}
+
 int run_compare(const SummaryIn &a, const SummaryIn &b, uint32_t min_cov, const CompareSnpIn &snp, CompareBuffers &B,
                 isx_compare_level *host_out, float *ms)
 {

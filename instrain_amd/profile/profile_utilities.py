@@ -898,12 +898,13 @@ class _BatchRun:
     released on the pipe that issued it -- the pipe is only replaced while nothing is in flight."""
 
     def __init__(self, bf, plan, refs, opt, make_pipe, depth, codes_of, est_segs, out, stage, bam=None, mm_values=None, mm_clamped=None,
-                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None, genomes=None):
+                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None, genomes=None, compare_set=None, compare_sample=None):
         self.bf, self.plan, self.refs, self.opt, self.make_pipe, self.depth = bf, plan, refs, opt, make_pipe, depth
         self.codes_of, self.est_segs, self.out, self.stage, self.bam = codes_of, est_segs, out, stage, bam
         self.mm_values, self.mm_clamped, self.gset, self.logs = mm_values, mm_clamped, gset, logs
         self.scaffold_tables, self.scaffold_levels = scaffold_tables, scaffold_levels
         self.genomes = genomes                       # genome_utilities.GenomeTables (profile_bam(stb=...)) or None
+        self.compare_set, self.compare_sample = compare_set, compare_sample    # compare.SampleSet that gets every batch's sketch, or None
         self.ekw = dict(opt.filter, skip_mm=opt.skip_mm, window_length=opt.window_length)
         self.pipe = self.cap = None
         self.in_flight = []                          # submitted, not yet collected (at most `depth`)
@@ -968,12 +969,14 @@ class _BatchRun:
                                       min_cov=opt.min_cov, started=g.t_submit, mm_clamped=self.mm_clamped, mm_values=self.mm_values)
             summaries = self.scaffold_tables is not None or self.scaffold_levels is not None or self.genomes is not None
             genes = self.gset is not None and bool(splits)
-            if summaries or genes:
+            if summaries or genes or self.compare_set is not None:
                 sb = np.r_[0, np.cumsum([self.refs[tid][1] for tid in g.tids])]
                 if summaries:
                     self.summarize(g, res["slot"], splits, sb)
                 if genes:
                     self.profile_genes(g, res["slot"], splits, sb)
+                if self.compare_set is not None:    # the slot's sketch (compare.SampleSet) before the slot goes back to the pipe
+                    self.compare_set.add_batch(self.compare_sample, res["slot"], [self.plan[k][1] for k in g.items], sb, self.mm_values)
         finally:
             self.pipe.release(t)
             g.ticket = None
@@ -1113,6 +1116,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     `stb` (scaffold -> genome, a dict or the path of a two-column tab-separated file) with `genome_tables` (dict that receives
     genome_info, scaffold2bin and bin2length: genomeUtilities.genomeLevel_from_IS from per-batch device roll-ups,
     genome_utilities.GenomeTables; scaffolds the stb does not name are left out, a genome may span batches; without `stb` no such call is made),
+    `compare_set` (a compare.SampleSet on the same ctx) with `compare_sample` (this BAM's name in it, default: the path): every batch's
+    sketch is added to the set before its slot is released (SampleSet.add_batch; without `compare_set` no such call is made),
     `batch_positions` / `batch_reads` (size of a device batch; `batch_observations` is accepted as 150 x batch_reads), `pipe_depth` (device batches in flight: the front end
     prepares batch k + 1 while batch k is profiled and its tables are cut), `stats` (dict that receives stage times).
     The BAM's reads go to the device as read segments (isx_pipe_submit_bam on a read-level pipe): the host never expands a
@@ -1168,7 +1173,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
             genomes = genome_utilities.GenomeTables(kwargs['stb'], {name: len(seq) for name, seq in s2s.items()})      # scaffold2length
         run = _BatchRun(bf, plan, refs, opt, functools.partial(open_pipe, ctx, opt, n_mm, depth), depth, codes_of, est_segs, out, stage,
                         bam=bam, mm_values=mm_values, mm_clamped=mm_clamped, gset=gset, logs=logs,
-                        scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'), genomes=genomes)
+                        scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'), genomes=genomes,
+                        compare_set=kwargs.get('compare_set'), compare_sample=kwargs.get('compare_sample', bam))
         # the pipe (pinned staging, device arena: tens of ms) is set up by one helper thread while another lays the groups out
         # (sequence codes, split tables: Python + numpy) -- a group's layout is then ready when the group before it is being handed
         # over (isx_pipe_submit_bam runs without the GIL)
