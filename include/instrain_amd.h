@@ -339,6 +339,70 @@ typedef struct {
 int isx_ld_level_sums(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_ld, const isx_ld *ld,
                       int32_t n_levels, isx_ld_level *out, float *device_ms);
 
+/* ---- iRep (irep_utilities.py:22-81 calculate_iRep_from_coverage_array as genomeLevel_coverage_info :297-365 calls it) ----
+ * A genome's coverage array is its scaffolds, longest first (ties: the caller's order), each without mask_edges positions at either
+ * end, laid end to end (length L).  iRep's windows are ISX_IREP_WINDOW positions every ISX_IREP_SLIDE: window w is the sum of
+ * ISX_IREP_WINDOW / ISX_IREP_SLIDE consecutive BLOCKS of ISX_IREP_SLIDE positions -- the scheme needs the slide to divide the window
+ * -- and block sums add over scaffolds and batches.  isx_irep_add adds a batch's share of the block sums (integer atomics: exact,
+ * order independent), isx_irep_finish runs the per-genome tail on the device. */
+#define ISX_IREP_WINDOW 5000
+#define ISX_IREP_SLIDE 100              /* must divide ISX_IREP_WINDOW */
+typedef struct {
+    int64_t L;                          /* masked, concatenated length */
+    int64_t n_blocks, n_windows;        /* ceil(L / slide); L >= window ? (L - window) / slide + 1 : 0 */
+    int64_t first_block, first_window;  /* in the flat block / window arrays of the set: no block belongs to two genomes */
+    int32_t first_scaffold;             /* where the genome's scaffolds begin in `order` */
+    int32_t num_contigs;                /* all its scaffolds, those the mask drops included */
+} isx_irep_genome;
+
+/* Host only.  scaffold_genome[i] in [-1, n_genomes) (-1 = in no genome).  genomes[n_genomes]; order[n_scaffolds]: the scaffolds genome
+ * by genome in concatenation order, then those of no genome; scaffold_offset[n_scaffolds]: where the scaffold's first unmasked
+ * position lies in its genome's array, -1 when the mask drops it (length < 2 * mask_edges) or it is in no genome. */
+int isx_irep_layout(int32_t n_scaffolds, const int64_t *scaffold_lengths, const int32_t *scaffold_genome, int32_t n_genomes,
+                    int32_t mask_edges, isx_irep_genome *genomes, int32_t *order, int64_t *scaffold_offset);
+
+#define ISX_IREP_FAIL_KEPT 1u           /* kept_windows < 0.98 */
+#define ISX_IREP_FAIL_COV 2u            /* avg_cov < 5 */
+#define ISX_IREP_FAIL_R2 4u             /* r2 < 0.9 */
+#define ISX_IREP_FAIL_FRAG 8u           /* fragMbp > 175 (always when L < ISX_IREP_WINDOW) */
+#define ISX_IREP_EMPTY 16u              /* L == 0: the reference raises, every value is NaN */
+#define ISX_IREP_NO_FIT 32u             /* fewer than three points after trimming: no line */
+typedef struct {
+    int64_t L, n_windows, n_kept;
+    uint64_t sum_cov;                   /* exact */
+    double avg_cov, fragMbp, kept_windows, r2;
+    double raw_irep;                    /* unfiltered_raw_iRep */
+    double gc_irep;                     /* unfiltered_iRep: the same fit on the GC-corrected coverage (_iRep_gc_bias :268-294) */
+    double irep;                        /* raw_irep, NaN when flags != 0 */
+    int32_t num_contigs;
+    uint32_t flags;                     /* ISX_IREP_* */
+} isx_irep_row;
+
+typedef struct isx_irep isx_irep;
+/* uploads the layout, zeroes one uint64 coverage sum and one uint32 G+C count per block and one seen flag per scaffold */
+int isx_irep_create(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_lengths, const int32_t *scaffold_genome, int32_t n_genomes,
+                    int32_t mask_edges, isx_irep **out);
+void isx_irep_destroy(isx_irep *irep);
+/* *n_blocks = blocks of the whole set, *n_scaffolds / *n_genomes as created (any pointer may be NULL) */
+int isx_irep_sizes(isx_irep *irep, int64_t *n_blocks, int32_t *n_scaffolds, int32_t *n_genomes);
+/* Adds a batch: set_index[i] = the set's scaffold that batch scaffold i is (same length), -1 = none of them.  level = the device level
+ * up to which coverage is cumulated (the batch's highest level whose real mm is <= 1; the last one without mm profiling), -1 = the
+ * batch has no such level: only G+C counts and seen flags are added.  A position adds its coverage, and 1 to the G+C count when the
+ * batch's resident reference has G or C there (anything but A/C/G/T counts 0).  Needs a completed isx_batch_run / a collected
+ * pipe slot; a lean slot and a scaffold added before are ISX_ERR_STATE.  Every argument is checked before anything is launched. */
+int isx_irep_add(isx_irep *irep, isx_batch *batch, int32_t n_scaffolds, const int64_t *scaffold_bounds, const int32_t *set_index,
+                 int32_t level, float *device_ms);
+/* the block arrays and seen flags home / a host copy (another rank's partial) added into the device's: cov[n_blocks],
+ * gc[n_blocks], seen[n_scaffolds]; a scaffold seen on both sides is ISX_ERR_STATE */
+int isx_irep_blocks_fetch(isx_irep *irep, uint64_t *cov, uint32_t *gc, uint8_t *seen);
+int isx_irep_blocks_add(isx_irep *irep, const uint64_t *cov, const uint32_t *gc, const uint8_t *seen);
+/* out[n_genomes].  Integer window sums, a segmented sort, the doubled median, the kept range (S > 0, 16 S >= med2, 2 S <= 8 med2:
+ * the reference's float test done exactly), X_i = int(i * (L / n_kept)) + 1, Y_i = log2(S_i / window), int(n_kept * 0.05) points
+ * trimmed at either end, a centred two-pass least-squares line in fp64 summed in a fixed tree: two calls return identical bytes.
+ * Then the GC stage on the kept windows: window G+C = sum of its blocks' counts / window, a line coverage = m gc + b, the windows whose
+ * |error| reaches the int(n * 0.01)-th largest dropped, the line again, every window shifted by mean - (m gc + b), sorted, fitted. */
+int isx_irep_finish(isx_irep *irep, isx_irep_row *out, float *device_ms);
+
 /* ---- compare: two samples on the same scaffolds (readComparer.py:35-143 compare_scaffold, one pair) ----
  * Two batches over the SAME flat space (same scaffolds laid out identically, same ctx).  One row per
  * (scaffold, mm): positions where both / either sample reach min_cov in the coverage cumulated over

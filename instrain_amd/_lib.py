@@ -145,6 +145,15 @@ COMPARE_SNP_DT = np.dtype([("gpos", "<u4"), ("mm", "<u2"), ("consensus_snp", "u1
                            ("has_a", "u1"), ("has_b", "u1"), ("con_a", "u1"), ("ref_a", "u1"), ("var_a", "u1"),
                            ("con_b", "u1"), ("ref_b", "u1"), ("var_b", "u1"), ("cnt_a", "<u4", (4,)), ("cnt_b", "<u4", (4,))])
 assert COMPARE_SNP_DT.itemsize == 48
+# iRep (include/instrain_amd.h isx_irep_genome / isx_irep_row)
+IREP_WINDOW, IREP_SLIDE = 5000, 100
+IREP_GENOME_DT = np.dtype([("L", "<i8"), ("n_blocks", "<i8"), ("n_windows", "<i8"), ("first_block", "<i8"), ("first_window", "<i8"),
+                           ("first_scaffold", "<i4"), ("num_contigs", "<i4")])
+IREP_ROW_DT = np.dtype([("L", "<i8"), ("n_windows", "<i8"), ("n_kept", "<i8"), ("sum_cov", "<u8"), ("avg_cov", "<f8"), ("fragMbp", "<f8"),
+                        ("kept_windows", "<f8"), ("r2", "<f8"), ("raw_irep", "<f8"), ("gc_irep", "<f8"), ("irep", "<f8"),
+                        ("num_contigs", "<i4"), ("flags", "<u4")])
+assert IREP_GENOME_DT.itemsize == 48 and IREP_ROW_DT.itemsize == 96
+IREP_FAIL_KEPT, IREP_FAIL_COV, IREP_FAIL_R2, IREP_FAIL_FRAG, IREP_EMPTY, IREP_NO_FIT = 1, 2, 4, 8, 16, 32       # isx_irep_row.flags
 CMPSET_TILE_DT = np.dtype([("word0", "<i8"), ("n_words", "<i4"), ("scaffold", "<i4")])      # isx_cmpset_tile
 CMPSET_MAX_LEVELS = 128         # ISX_CMPSET_MAX_LEVELS
 
@@ -172,6 +181,7 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_batch_fetch_entries", "isx_batch_fetch_dense", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs",
            "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
            "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
+           "isx_irep_layout", "isx_irep_create", "isx_irep_destroy", "isx_irep_sizes", "isx_irep_add", "isx_irep_blocks_fetch", "isx_irep_blocks_add", "isx_irep_finish",
            "isx_genes_create", "isx_genes_destroy", "isx_genes_sites", "isx_batch_profile_genes", "isx_genes_profile_snvs",
            "isx_pipe_create", "isx_pipe_destroy", "isx_pipe_submit", "isx_pipe_submit_reads", "isx_pipe_stage_reads", "isx_pipe_submit_wire", "isx_wire_bytes", "isx_wire_free", "isx_wire_keep_reference", "isx_pipe_submit_bam", "isx_encode_segs", "isx_encode_segs_ring", "isx_seg_records_needed", "isx_encode_delta", "isx_delta_records_needed", "isx_count_read_segs", "isx_pack_reads", "isx_pipe_collect", "isx_pipe_release", "isx_pipe_fetch_entries", "isx_pipe_fetch_entries_shrunk", "isx_levels_expand", "isx_encode_obs", "isx_encode_obs_ring",
            "isx_pack_ref_planes", "isx_planes_from_segs", "isx_pack_read_planes", "isx_pipe_submit_planes", "isx_pipe_stage_planes", "isx_encode_planes", "isx_encode_planes_mm", "isx_pipe_set_reference_budget", "isx_host_register", "isx_host_unregister",
@@ -256,6 +266,15 @@ def load():
     lib.isx_cmpset_compare.argtypes = [vp, C.c_double, i64, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_pair_snps.argtypes = [vp, i32, i32, C.POINTER(i64)]
     lib.isx_cmpset_fetch_snps.argtypes = [vp, vp]
+    lib.isx_irep_layout.argtypes = [i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.isx_irep_create.argtypes = [vp, i32, vp, vp, i32, i32, C.POINTER(vp)]
+    lib.isx_irep_destroy.argtypes = [vp]
+    lib.isx_irep_destroy.restype = None
+    lib.isx_irep_sizes.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]
+    lib.isx_irep_add.argtypes = [vp, vp, i32, vp, vp, i32, C.POINTER(C.c_float)]
+    lib.isx_irep_blocks_fetch.argtypes = [vp, vp, vp, vp]
+    lib.isx_irep_blocks_add.argtypes = [vp, vp, vp, vp]
+    lib.isx_irep_finish.argtypes = [vp, vp, C.POINTER(C.c_float)]
     lib.isx_genes_create.argtypes = [vp, i64, vp, C.c_char_p, i64, C.POINTER(vp)]
     lib.isx_genes_destroy.argtypes = [vp]
     lib.isx_genes_destroy.restype = None

@@ -101,6 +101,57 @@ __global__ void __launch_bounds__(256) k_genome_hist(const uint32_t *cov, uint32
     flush();
 }
 
+// iRep's block sums (include/instrain_amd.h isx_irep_add): the tiles of k_genome_hist; sbase[sc] = where the scaffold's first unmasked
+// position lies in the set's block space (its genome's first block * ISX_IREP_SLIDE + its offset in the genome's array), -1 = the scaffold
+// adds nothing.  A wave's 64 consecutive positions touch at most two blocks (64 <= ISX_IREP_SLIDE): both partial sums are reduced inside
+// the wave and lane 0 issues at most two integer atomics per array.  cov == NULL: the G+C counts alone.
+static_assert(ISX_IREP_SLIDE >= 64, "a wave must not span more than two blocks");
+__global__ void __launch_bounds__(256) k_irep_blocks(const uint32_t *cov, uint32_t n_pos, const int64_t *sbounds, const int64_t *sbase,
+                                                     int n_scaf, int64_t mask, const uint8_t *ref, int ref_packed, const uint8_t *ref_n,
+                                                     unsigned long long *bcov, uint32_t *bgc)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t t0 = (int64_t)blockIdx.x * GH_TILE;
+    const int64_t t1 = min((int64_t)n_pos, t0 + (int64_t)GH_TILE);
+    // the loops below depend on the tile alone: whole waves stay together through the shuffles
+    for (int sc = scaf_of(sbounds, n_scaf, t0); sc < n_scaf; sc++) {
+        const int64_t s0 = sbounds[sc], s1 = sbounds[sc + 1];
+        if (s0 >= t1) break;
+        const int64_t base = sbase[sc];
+        if (base < 0 || s1 - s0 < 2 * mask) continue;
+        const int64_t lo = max(t0, s0 + mask), hi = min(t1, s1 - mask);
+        const int64_t shift = base - s0 - mask;                     // flat position -> position in the block space
+        for (int64_t w0 = lo + (tid - lane); w0 < hi; w0 += 256) {  // w0: the wave's first position
+            const int64_t p = w0 + lane;
+            const bool on = p < hi;
+            const int64_t q0 = (w0 + shift) / ISX_IREP_SLIDE;
+            const bool second = on && (p + shift) / ISX_IREP_SLIDE != q0;
+            unsigned long long c0 = 0, c1 = 0;
+            bool gc = false;
+            if (on) {
+                const unsigned long long c = cov ? cov[p] : 0u;
+                if (second) c1 = c; else c0 = c;
+                uint32_t code;
+                if (ref_packed == 2) code = (ref_n && ((ref_n[p >> 3] >> (p & 7)) & 1u)) ? 4u : (uint32_t)((ref[p >> 2] >> ((p & 3) << 1)) & 3u);
+                else code = ref[p];
+                gc = code == 1u || code == 3u;                      // codes: A C T G, anything else is no base
+            }
+            const uint32_t g0 = (uint32_t)__popcll(__ballot(gc && !second)), g1 = (uint32_t)__popcll(__ballot(gc && second));
+            if (cov)
+                for (int o = 32; o > 0; o >>= 1) {
+                    c0 += (unsigned long long)__shfl_xor((long long)c0, o);
+                    c1 += (unsigned long long)__shfl_xor((long long)c1, o);
+                }
+            if (lane == 0) {
+                if (c0) atomicAdd(&bcov[q0], c0);
+                if (c1) atomicAdd(&bcov[q0 + 1], c1);
+                if (g0) atomicAdd(&bgc[q0], g0);
+                if (g1) atomicAdd(&bgc[q0 + 1], g1);
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) k_snv_levels(const isx_snv *snv, uint32_t n, const int64_t *bounds, int n_seg, int n_levels,
                                                     uint32_t *out)
 {
@@ -177,6 +228,15 @@ void launch_genome_hist(hipStream_t s, const uint32_t *cov, uint32_t n_pos, cons
     const uint32_t tiles = (n_pos + GH_TILE - 1) / GH_TILE;
     hipLaunchKernelGGL(k_genome_hist, dim3(tiles), dim3(256), use_lds ? (size_t)hist_bins * 4 : 0, s, cov, n_pos, sbounds, sgen, n_scaf,
                        (int64_t)mask_edges, hist_bins, use_lds, acc, acc_stride, hist, hist_stride);
+}
+
+void launch_irep_blocks(hipStream_t s, const uint32_t *cov, uint32_t n_pos, const int64_t *sbounds, const int64_t *sbase, int n_scaf,
+                        int mask_edges, const uint8_t *ref, int ref_packed, const uint8_t *ref_n, uint64_t *block_cov, uint32_t *block_gc)
+{
+    if (!n_pos) return;
+    const uint32_t tiles = (n_pos + GH_TILE - 1) / GH_TILE;
+    hipLaunchKernelGGL(k_irep_blocks, dim3(tiles), dim3(256), 0, s, cov, n_pos, sbounds, sbase, n_scaf, (int64_t)mask_edges, ref, ref_packed,
+                       ref_n, reinterpret_cast<unsigned long long *>(block_cov), block_gc);
 }
 
 int run_snv_levels(int device, hipStream_t s, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_snv, const isx_snv *snv,

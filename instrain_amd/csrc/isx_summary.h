@@ -139,5 +139,19 @@ int run_genome_cov(const SummaryIn &in, SummaryBuffers &B, const int32_t *scaffo
                    isx_genome_cov *acc_out, uint32_t *hist_out, float *ms);
 int run_snv_levels(int device, hipStream_t s, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_snv, const isx_snv *snv,
                    int32_t n_levels, isx_snv_level *out, float *device_ms);
+// iRep's block sums of one batch (isx_irep_add): the coverage cumulated up to `level` (materialised as run_genome_cov does; -1: no
+// coverage, G+C counts only) and the batch's resident reference, added into the set's block arrays.  scaffold_base[n_scaffolds] (host):
+// where every batch scaffold's first unmasked position lies in the block space, -1 = adds nothing
+struct IrepAdd {
+    const int64_t *scaffold_base;
+    int level, mask_edges;
+    const uint8_t *ref, *ref_n;
+    int ref_packed;
+    uint64_t *block_cov;
+    uint32_t *block_gc;
+};
+void launch_irep_blocks(hipStream_t s, const uint32_t *cov, uint32_t n_pos, const int64_t *sbounds, const int64_t *sbase, int n_scaf,
+                        int mask_edges, const uint8_t *ref, int ref_packed, const uint8_t *ref_n, uint64_t *block_cov, uint32_t *block_gc);
+int run_irep_add(const SummaryIn &in, SummaryBuffers &B, const IrepAdd &a, float *ms);
 int run_ld_levels(int device, hipStream_t s, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_ld, const isx_ld *ld,
                   int32_t n_levels, isx_ld_level *out, float *device_ms);

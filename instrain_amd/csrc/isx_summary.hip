@@ -879,6 +879,51 @@ int run_genome_cov(const SummaryIn &in, SummaryBuffers &B, const int32_t *scaffo
     return done(ISX_OK);
 }
 
+// ---- iRep's block sums of one batch (isx_irep.hip isx_irep_add): the levels up to a.level are materialised as above, then one pass
+// over the positions (isx_genomes.hip k_irep_blocks) adds coverage and G+C counts into the set's blocks ----
+int run_irep_add(const SummaryIn &in, SummaryBuffers &B, const IrepAdd &a, float *ms)
+{
+    hipStream_t s = in.stream;
+    const uint32_t n_pos = in.n_pos;
+    const int n_scaf = in.n_scaffolds, M = in.M;
+    int rc;
+    B.fit_positions(n_pos);
+    if ((rc = dev_alloc(&B.cov, B.cap_pos)) || (rc = dev_alloc(&B.cv, B.cap_pos)) || (rc = dev_alloc(&B.cr, B.cap_pos))) return rc;
+    int64_t *d_sb = nullptr, *d_base = nullptr;
+    Acc *d_sacc = nullptr;
+    auto done = [&](int code) {
+        void *ps[] = {d_sb, d_base, d_sacc};
+        for (void *p : ps) if (p) isx_dev_free(p);
+        return code;
+    };
+#define IR_TRY(expr) do { if ((expr) != hipSuccess) { isx_set_error(std::string("HIP error in the iRep block pass: ") + #expr); return done(ISX_ERR_HIP); } } while (0)
+    IR_TRY(isx_raw_dev_malloc(&d_sb, ((size_t)n_scaf + 1) * sizeof(int64_t)));
+    IR_TRY(isx_raw_dev_malloc(&d_base, (size_t)n_scaf * sizeof(int64_t)));
+    IR_TRY(isx_raw_dev_malloc(&d_sacc, (size_t)n_scaf * sizeof(Acc)));
+    IR_TRY(hipMemcpyAsync(d_sb, in.scaffold_bounds, ((size_t)n_scaf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    IR_TRY(hipMemcpyAsync(d_base, a.scaffold_base, (size_t)n_scaf * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    IR_TRY(hipMemsetAsync(d_sacc, 0, (size_t)n_scaf * sizeof(Acc), s));
+    IR_TRY(hipEventRecord(in.ev[0], s));
+    const dim3 blk(256), gpos((n_pos + 255) / 256);
+    if (a.level >= 0) {
+        if (M == 1) launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
+        else {
+            IR_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
+            for (int mm = 0; mm <= a.level; mm++)
+                hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
+                                   (uint32_t)mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
+        }
+    }
+    launch_irep_blocks(s, a.level >= 0 ? B.cov : nullptr, n_pos, d_sb, d_base, n_scaf, a.mask_edges, a.ref, a.ref_packed, a.ref_n,
+                       a.block_cov, a.block_gc);
+    IR_TRY(hipGetLastError());
+    IR_TRY(hipEventRecord(in.ev[1], s));
+    IR_TRY(isx_wait_stream(s));
+#undef IR_TRY
+    if (ms) { float v = 0.f; (void)hipEventElapsedTime(&v, in.ev[0], in.ev[1]); *ms = v; }
+    return done(ISX_OK);
+}
+
 void CompareBuffers::release()
 {
     void *ps[] = {cov_a, cov_b, scratch_f, bounds, acc_a, acc_b, both, rows, keys, idx, cand, snp_rows, cursors, temp};

@@ -487,6 +487,87 @@ class Genes:
             pass
 
 
+def irep_layout(lengths, genome, n_genomes, mask_edges=100):
+    """isx_irep_layout (host only) -> (IREP_GENOME_DT [n_genomes], order int32 [n_scaffolds], offset int64 [n_scaffolds])"""
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    gn = np.ascontiguousarray(genome, dtype=np.int32)
+    if len(ln) != len(gn):
+        raise IsxError(-1, "irep_layout: one genome id per scaffold")
+    gen = np.zeros(max(int(n_genomes), 1), dtype=_lib.IREP_GENOME_DT)
+    order, off = np.zeros(max(len(ln), 1), dtype=np.int32), np.zeros(max(len(ln), 1), dtype=np.int64)
+    check(_lib.load().isx_irep_layout(len(ln), ln.ctypes.data, gn.ctypes.data, int(n_genomes), int(mask_edges), gen.ctypes.data,
+                                      order.ctypes.data, off.ctypes.data))
+    return gen[:int(n_genomes)], order[:len(ln)], off[:len(ln)]
+
+
+class IRep:
+    """iRep of a run's genomes on the device (isx_irep_*): lengths / genome (0..n_genomes-1, -1 = in no genome) of the run's scaffolds
+    in the caller's order.  add() takes every batch once, blocks() / add_blocks() move partial block sums between accumulators
+    (ranks), finish() -> IREP_ROW_DT [n_genomes]."""
+
+    def __init__(self, ctx, lengths, genome, n_genomes, mask_edges=100):
+        self.ctx, self.lib = ctx, ctx.lib
+        ln = np.ascontiguousarray(lengths, dtype=np.int64)
+        gn = np.ascontiguousarray(genome, dtype=np.int32)
+        if len(ln) != len(gn):
+            raise IsxError(-1, "IRep: one genome id per scaffold")
+        self.n_scaffolds, self.n_genomes = len(ln), int(n_genomes)
+        h = C.c_void_p()
+        check(self.lib.isx_irep_create(ctx.h, len(ln), ln.ctypes.data, gn.ctypes.data, int(n_genomes), int(mask_edges), C.byref(h)))
+        self.h = h
+        nb = C.c_int64(0)
+        check(self.lib.isx_irep_sizes(self.h, C.byref(nb), None, None))
+        self.n_blocks = int(nb.value)
+        ctx._adopt(self)
+
+    def add(self, batch, scaffold_bounds, set_index, level):
+        """a run Batch or a collected pipe slot: set_index[i] = which of the accumulator's scaffolds batch scaffold i is (-1: none);
+        level = the device level coverage is cumulated up to, -1 = G+C counts and seen flags only -> device ms"""
+        sb = np.ascontiguousarray(scaffold_bounds, dtype=np.int64)
+        si = np.ascontiguousarray(set_index, dtype=np.int32)
+        if len(si) != len(sb) - 1:
+            raise IsxError(-1, "IRep.add: one set index per scaffold")
+        ms = C.c_float(0)
+        check(self.lib.isx_irep_add(self.h, batch.h, len(sb) - 1, sb.ctypes.data, si.ctypes.data, int(level), C.byref(ms)))
+        return ms.value
+
+    def blocks(self):
+        """-> (uint64 coverage sums [n_blocks], uint32 G+C counts [n_blocks], uint8 seen [n_scaffolds])"""
+        cov, gc = np.zeros(max(self.n_blocks, 1), dtype=np.uint64), np.zeros(max(self.n_blocks, 1), dtype=np.uint32)
+        seen = np.zeros(max(self.n_scaffolds, 1), dtype=np.uint8)
+        check(self.lib.isx_irep_blocks_fetch(self.h, cov.ctypes.data, gc.ctypes.data, seen.ctypes.data))
+        return cov[:self.n_blocks], gc[:self.n_blocks], seen[:self.n_scaffolds]
+
+    def add_blocks(self, cov, gc=None, seen=None):
+        """adds a host copy (another accumulator's blocks(), or sums a test laid out) into the device's arrays"""
+        cov = np.ascontiguousarray(cov, dtype=np.uint64)
+        gc = np.zeros(len(cov), dtype=np.uint32) if gc is None else np.ascontiguousarray(gc, dtype=np.uint32)
+        seen = np.zeros(self.n_scaffolds, dtype=np.uint8) if seen is None else np.ascontiguousarray(seen, dtype=np.uint8)
+        if len(cov) != self.n_blocks or len(gc) != self.n_blocks or len(seen) != self.n_scaffolds:
+            raise IsxError(-1, "IRep.add_blocks: %d blocks and %d scaffolds expected" % (self.n_blocks, self.n_scaffolds))
+        pad = np.zeros(1, dtype=np.uint64)          # (a set without blocks still hands over valid pointers)
+        check(self.lib.isx_irep_blocks_add(self.h, (cov if len(cov) else pad).ctypes.data, (gc if len(gc) else pad).ctypes.data,
+                                           (seen if len(seen) else pad).ctypes.data))
+
+    def finish(self):
+        """-> (IREP_ROW_DT [n_genomes], device ms)"""
+        out = np.zeros(max(self.n_genomes, 1), dtype=_lib.IREP_ROW_DT)
+        ms = C.c_float(0)
+        check(self.lib.isx_irep_finish(self.h, out.ctypes.data, C.byref(ms)))
+        return out[:self.n_genomes], ms.value
+
+    def close(self):
+        if self.h:
+            self.lib.isx_irep_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _SlotBatch(Batch):
     """A collected pipe slot seen as a Batch (fetch of entries / ld rows, summaries); owned by the pipe."""
 

@@ -6,11 +6,11 @@ the device's per-genome aggregates of ONE batch whose genomes are consecutive sc
 
 GenomeTables: the whole genome-level table, genomeLevel_from_IS (:145-269), from per-batch device roll-ups that only ever ADD
 (engine.Batch.summarize / genome_coverage, engine.snv_level_counts / ld_level_sums), so a genome may be any subset of the scaffolds
-and may span batches.  iRep is not part of the hot path: its columns are NaN here."""
+and may span batches.  iRep comes from the device too (engine.IRep, finished once per run): set_irep() takes its rows."""
 import numpy as np
 import pandas as pd
 
-from .._lib import GENOME_COV_DT, LD_LEVEL_DT, SNV_LEVEL_DT
+from .._lib import GENOME_COV_DT, IREP_EMPTY, LD_LEVEL_DT, SNV_LEVEL_DT
 
 
 def genome_level_rows(levels, genomes, mms=None):
@@ -73,8 +73,9 @@ class GenomeTables:
     true_scaffolds only, prepare_genome_wide :129-139).  add_batch() takes a batch's per-(scaffold, level) device rows and its
     per-genome coverage distribution; genome_info() makes the reference's table.
 
-    Not produced: iRep / iRep_GC_corrected (NaN) and the reads_* / filtered_read_pair_count columns of the reference's table (they
-    come from a per-scaffold mapping_info, which this package does not make yet)."""
+    iRep / iRep_GC_corrected are NaN until set_irep() brought the finished rows of an engine.IRep built on irep_scaffolds().
+    Not produced: the reads_* / filtered_read_pair_count columns of the reference's table (they come from a per-scaffold
+    mapping_info, which this package does not make yet)."""
 
     def __init__(self, stb, scaffold2length, mask_edges=100):
         self.stb = parse_stb(stb)
@@ -96,6 +97,7 @@ class GenomeTables:
         self._ld = None                     # [G + 1, n_levels] LD_LEVEL_DT; the last row collects scaffolds the stb does not name
         self._acc = None                    # [G, n_levels] GENOME_COV_DT
         self._hist = None                   # [G, n_levels, bins] int64
+        self._irep = None                   # [G] IREP_ROW_DT (set_irep) or None: both iRep columns NaN
 
     def batch_genomes(self, names):
         """-> (genome id of every scaffold for engine.Batch.genome_coverage, -1 = none; the genomes those ids stand for).
@@ -106,6 +108,39 @@ class GenomeTables:
             if g is not None and sc in self.s2l:
                 ids[i] = local.setdefault(g, len(local))
         return ids, list(local)
+
+    def irep_scaffolds(self):
+        """-> (names, lengths, genome index) of the scaffolds an engine.IRep of this run is built on: those the stb names AND that
+        have a length (genomeUtilities.py:312), in the stb's order -- the order ties between equal lengths fall back to"""
+        names = [sc for sc in self.stb if sc in self.s2l]
+        return (names, np.array([int(self.s2l[sc]) for sc in names], dtype=np.int64),
+                np.array([self.gidx[self.stb[sc]] for sc in names], dtype=np.int32))
+
+    def irep_level(self, mms, n_levels, skip_mm_profiling=False):
+        """the `level` of engine.IRep.add for a batch of n_levels device levels whose real mm values are mms (None: the ranks):
+        the highest level whose mm is <= 1 (maxMM == 1, genomeUtilities.py:331-334), the last one under skip_mm_profiling, -1 = none"""
+        if skip_mm_profiling:
+            return int(n_levels) - 1
+        mms = np.arange(n_levels, dtype=np.int64) if mms is None else np.asarray(mms, dtype=np.int64)
+        return int(np.searchsorted(mms, 1, side="right")) - 1
+
+    def set_irep(self, rows):
+        """rows: IREP_ROW_DT [n_genomes] of engine.IRep.finish(), genomes in self.genomes' order"""
+        rows = np.asarray(rows)
+        if rows.shape != (len(self.genomes),):
+            raise ValueError("GenomeTables.set_irep: one row per genome expected")
+        self._irep = rows.copy()
+
+    def irep_accessory(self):
+        """one row per genome with the keys of the reference's accessory dict (irep_utilities.py:33-66)"""
+        if self._irep is None:
+            raise ValueError("GenomeTables.irep_accessory: no iRep rows were set")
+        r = self._irep
+        flag = np.where((r["flags"] & IREP_EMPTY) != 0, np.nan, 1.0)
+        return pd.DataFrame({"genome": self.genomes, "kept_windows": r["kept_windows"], "avg_cov": r["avg_cov"], "r2": r["r2"],
+                             "fragMbp": r["fragMbp"], "unfiltered_raw_iRep": r["raw_irep"],
+                             "iRep_GC_corrected": pd.Series([np.nan if np.isnan(f) else True for f in flag], dtype=object),
+                             "unfiltered_iRep": r["gc_irep"]})
 
     def _levels(self, mms, n):
         mms = np.arange(n, dtype=np.int64) if mms is None else np.asarray(mms, dtype=np.int64)
@@ -269,6 +304,14 @@ class GenomeTables:
         db = pd.DataFrame(table)
         db["iRep"] = np.nan
         db["iRep_GC_corrected"] = np.nan
+        # iRep is computed once per genome, at maxMM == 1 (all levels under skip_mm_profiling), and goes into every row of the
+        # genome; a table without an mm == 1 row never computes it (genomeUtilities.py:324-361).  The flag is True whenever the
+        # computation ran with GC windows, NaN when it raised (an empty genome array)
+        if self._irep is not None and len(db) and (skip_mm or 1 in mms):
+            gi = np.array([self.gidx[g] for g in db["genome"]], dtype=np.int64)
+            db["iRep"] = self._irep["irep"][gi]
+            empty = (self._irep["flags"][gi] & IREP_EMPTY) != 0
+            db["iRep_GC_corrected"] = pd.Series([np.nan if e else True for e in empty], dtype=object, index=db.index)
         return db, levels, mms
 
     # -- linkage half (_genome_wide_linkage :636-659) --

@@ -898,13 +898,15 @@ class _BatchRun:
     released on the pipe that issued it -- the pipe is only replaced while nothing is in flight."""
 
     def __init__(self, bf, plan, refs, opt, make_pipe, depth, codes_of, est_segs, out, stage, bam=None, mm_values=None, mm_clamped=None,
-                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None, genomes=None, compare_set=None, compare_sample=None):
+                 gset=None, logs=None, scaffold_tables=None, scaffold_levels=None, genomes=None, compare_set=None, compare_sample=None,
+                 irep=None, irep_index=None):
         self.bf, self.plan, self.refs, self.opt, self.make_pipe, self.depth = bf, plan, refs, opt, make_pipe, depth
         self.codes_of, self.est_segs, self.out, self.stage, self.bam = codes_of, est_segs, out, stage, bam
         self.mm_values, self.mm_clamped, self.gset, self.logs = mm_values, mm_clamped, gset, logs
         self.scaffold_tables, self.scaffold_levels = scaffold_tables, scaffold_levels
         self.genomes = genomes                       # genome_utilities.GenomeTables (profile_bam(stb=...)) or None
         self.compare_set, self.compare_sample = compare_set, compare_sample    # compare.SampleSet that gets every batch's sketch, or None
+        self.irep, self.irep_index = irep, irep_index or {}    # engine.IRep of the run's genomes (scaffold name -> its index there), or None
         self.ekw = dict(opt.filter, skip_mm=opt.skip_mm, window_length=opt.window_length)
         self.pipe = self.cap = None
         self.in_flight = []                          # submitted, not yet collected (at most `depth`)
@@ -1014,6 +1016,9 @@ class _BatchRun:
         acc = hist = None
         if local:
             acc, hist, _ = slot.genome_coverage(sb, ids, len(local), mask_edges=self.genomes.mask_edges)
+        if self.irep is not None:                   # iRep's block sums: coverage up to mm == 1 (every level without mm profiling)
+            self.irep.add(slot, sb, [self.irep_index.get(name, -1) for name in names],
+                          self.genomes.irep_level(self.mm_values, n_levels, self.opt.skip_mm))
         self.genomes.add_batch(names, [self.refs[tid][1] for tid in g.tids], levels, snv_levels, ld_levels, local, acc, hist,
                                mms=self.mm_values)
         return snv_levels
@@ -1115,7 +1120,10 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     genes_coverage, genes_clonality, genes_SNP_count and SNP_mutation_types: the gene pass, gene_profile.py, on every batch),
     `stb` (scaffold -> genome, a dict or the path of a two-column tab-separated file) with `genome_tables` (dict that receives
     genome_info, scaffold2bin and bin2length: genomeUtilities.genomeLevel_from_IS from per-batch device roll-ups,
-    genome_utilities.GenomeTables; scaffolds the stb does not name are left out, a genome may span batches; without `stb` no such call is made),
+    genome_utilities.GenomeTables; scaffolds the stb does not name are left out, a genome may span batches; without `stb` no such call is made;
+    its iRep / iRep_GC_corrected columns come from an engine.IRep that gets every batch and is finished once; `irep=False` skips all of
+    that, `irep_accessory=True` also puts `iRep_accessory` into genome_tables: one row per genome of kept_windows, avg_cov, r2, fragMbp,
+    unfiltered_raw_iRep, iRep_GC_corrected and unfiltered_iRep),
     `compare_set` (a compare.SampleSet on the same ctx) with `compare_sample` (this BAM's name in it, default: the path): every batch's
     sketch is added to the set before its slot is released (SampleSet.add_batch; without `compare_set` no such call is made),
     `batch_positions` / `batch_reads` (size of a device batch; `batch_observations` is accepted as 150 x batch_reads), `pipe_depth` (device batches in flight: the front end
@@ -1129,7 +1137,7 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     stage = _StageClock(kwargs.get('stats'))
     own_ctx = kwargs.get('ctx') is None
     own_bf = kwargs.get('bamfile') is None           # a caller's handle may already hold the scan (dist.profile_bam_sharded)
-    ctx = bf = run = helpers = gset = None
+    ctx = bf = run = helpers = gset = irep = None
     codes_of, layouts = [], []
     if kwargs.get('genes') is None and kwargs.get('gene_file'):        # a gene file the run cannot use is the caller's error, not a split's
         kwargs['genes'] = gene_profile.parse_genes(kwargs['gene_file'])
@@ -1171,10 +1179,17 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
         genomes = None
         if kwargs.get('stb') is not None:
             genomes = genome_utilities.GenomeTables(kwargs['stb'], {name: len(seq) for name, seq in s2s.items()})      # scaffold2length
+        irep_index = None
+        if genomes is not None and kwargs.get('irep', True):
+            i_names, i_lengths, i_genome = genomes.irep_scaffolds()
+            if i_names:
+                irep = engine.IRep(ctx, i_lengths, i_genome, len(genomes.genomes), mask_edges=genomes.mask_edges)
+                irep_index = {name: i for i, name in enumerate(i_names)}
         run = _BatchRun(bf, plan, refs, opt, functools.partial(open_pipe, ctx, opt, n_mm, depth), depth, codes_of, est_segs, out, stage,
                         bam=bam, mm_values=mm_values, mm_clamped=mm_clamped, gset=gset, logs=logs,
                         scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'), genomes=genomes,
-                        compare_set=kwargs.get('compare_set'), compare_sample=kwargs.get('compare_sample', bam))
+                        compare_set=kwargs.get('compare_set'), compare_sample=kwargs.get('compare_sample', bam),
+                        irep=irep, irep_index=irep_index)
         # the pipe (pinned staging, device arena: tens of ms) is set up by one helper thread while another lays the groups out
         # (sequence codes, split tables: Python + numpy) -- a group's layout is then ready when the group before it is being handed
         # over (isx_pipe_submit_bam runs without the GIL)
@@ -1186,6 +1201,10 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
         if genomes is not None and kwargs.get('genome_tables') is not None:
             gt = kwargs['genome_tables']
             gt['scaffold2bin'], gt['bin2length'] = genomes.stb, genomes.bin2length
+            if irep is not None:
+                genomes.set_irep(irep.finish()[0])
+                if kwargs.get('irep_accessory'):
+                    gt['iRep_accessory'] = genomes.irep_accessory()
             gt['genome_info'] = genomes.genome_info(skip_mm_profiling=opt.skip_mm)
         if gset is not None:
             gene_profile.finish_genes(gset, kwargs['gene_tables'] if kwargs.get('gene_tables') is not None else {})
@@ -1209,6 +1228,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
             helpers.shutdown(wait=True)
         if gset is not None:
             gset.close()
+        if irep is not None:
+            irep.close()
         # this call's own large arrays (sequence codes, group layouts) go before the helper thread below starts unmapping the pipe's
         # and the handle's gigabytes: both want the process' address-space lock
         del codes_of[:], layouts[:]
