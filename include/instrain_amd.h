@@ -229,6 +229,10 @@ int isx_batch_launch(isx_batch *b);
 int isx_batch_wait(isx_batch *b);
 int isx_batch_sizes(const isx_batch *b, isx_sizes *out);
 int isx_batch_timings(const isx_batch *b, isx_timings *out);
+/* Which chain the linkage stages of the last pass took: 3 = bucket chain, 1 = sorted chain (ISX_LINK_CHAIN=sorted, or the bucket chain's
+ * fallback for a site with more unique keys than its table holds), 2 = dense int8 MFMA path (linkage_mode 2), 0 = none (linkage off, no
+ * SNP site or no allele observation).  Negative: an error code (not run yet). */
+int isx_batch_link_chain(const isx_batch *b);
 
 /* Results -> caller-allocated host buffers sized from isx_batch_sizes. Tables come back in
  * canonical order: entries (gpos, mm); snv (gpos, mm); ld (gpos_a, gpos_b, mm). */

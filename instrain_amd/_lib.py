@@ -177,7 +177,7 @@ class IsxError(RuntimeError):
 
 
 SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destroy", "isx_ctx_reserve_cus", "isx_set_null_model",
-           "isx_batch_create", "isx_batch_create_reads", "isx_batch_destroy", "isx_batch_run", "isx_batch_launch", "isx_batch_wait", "isx_batch_sizes", "isx_batch_timings",
+           "isx_batch_create", "isx_batch_create_reads", "isx_batch_destroy", "isx_batch_run", "isx_batch_launch", "isx_batch_wait", "isx_batch_sizes", "isx_batch_timings", "isx_batch_link_chain",
            "isx_batch_fetch_entries", "isx_batch_fetch_dense", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs",
            "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
            "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
@@ -243,6 +243,7 @@ def load():
     lib.isx_batch_wait.argtypes = [vp]
     lib.isx_batch_sizes.argtypes = [vp, C.POINTER(Sizes)]
     lib.isx_batch_timings.argtypes = [vp, C.POINTER(Timings)]
+    lib.isx_batch_link_chain.argtypes = [vp]
     for f in ("isx_batch_fetch_entries", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs"):
         getattr(lib, f).argtypes = [vp, vp]
     lib.isx_batch_fetch_dense.argtypes = [vp, vp, vp, vp]

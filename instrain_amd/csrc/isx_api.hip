@@ -1665,6 +1665,13 @@ int isx_batch_sizes(const isx_batch *b, isx_sizes *out)
     return ISX_OK;
 }
 
+int isx_batch_link_chain(const isx_batch *b)
+{
+    if (!b) { isx_set_error("isx_batch_link_chain: bad argument"); return ISX_ERR_ARG; }
+    if (!b->ran) { isx_set_error("isx_batch_link_chain: run the batch first"); return ISX_ERR_STATE; }
+    return b->link_chain;
+}
+
 int isx_batch_timings(const isx_batch *b, isx_timings *out)
 {
     if (!b || !out) { isx_set_error("isx_batch_timings: bad argument"); return ISX_ERR_ARG; }

@@ -288,6 +288,13 @@ class Batch:
         check(self.lib.isx_batch_sizes(self.h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in Sizes._fields_}
 
+    def link_chain(self):
+        """which chain the linkage stages of the last pass took (isx_batch_link_chain): 3 bucket, 1 sorted, 2 dense MFMA, 0 none"""
+        rc = self.lib.isx_batch_link_chain(self.h)
+        if rc < 0:
+            check(rc)
+        return int(rc)
+
     def timings(self):
         t = Timings()
         check(self.lib.isx_batch_timings(self.h, C.byref(t)))

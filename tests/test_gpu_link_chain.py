@@ -28,8 +28,10 @@ def _run(ctx, w, n_mm_bins, **kw):
     b = engine.Batch(ctx, w["ref_codes"], w["split_bounds"], w["obs"], w["pair"], n_mm_bins=n_mm_bins, enable_linkage=True, **kw)
     b.run()
     f, s = b.fetch(), b.sizes()
+    s["link_chain"] = b.link_chain()            # which chain ran: 3 bucket, 1 sorted, 2 dense MFMA, 0 none
     b.run()                                     # the same batch again: the chain's tables are reused (epoch-tagged heads)
     f2 = b.fetch()
+    assert b.link_chain() == s["link_chain"]
     b.close()
     assert f["ld"].tobytes() == f2["ld"].tobytes()
     return f, s
@@ -55,6 +57,7 @@ def test_bucket_chain_equals_sorted_chain(ctx, monkeypatch, skip_mm, cov, sites)
     exp = _run(ctx, w, M)
     assert exp[1]["n_ld"] > (1000 if cov >= 60 else 50) and exp[1]["n_edges"] >= exp[1]["n_ld"] // (M + 1)
     _same(got, exp, "bucket vs sorted")
+    assert got[1]["link_chain"] == 3 and exp[1]["link_chain"] == 1
 
 
 def test_site_with_too_many_keys_takes_the_sorted_chain(ctx, monkeypatch):
@@ -67,6 +70,7 @@ def test_site_with_too_many_keys_takes_the_sorted_chain(ctx, monkeypatch):
     monkeypatch.setenv("ISX_LINK_MAXU", "2")
     got = _run(ctx, w, 1)
     _same(got, exp, "fallback")
+    assert got[1]["link_chain"] == 1 and exp[1]["link_chain"] == 1          # (the fallback happened: the sorted chain made these rows)
     assert exp[1]["n_ld"] > 100
 
 
@@ -78,9 +82,11 @@ def test_chain_tables_grow(ctx, monkeypatch):
     monkeypatch.setenv("ISX_LINK_TEST_CAPS", "16,4")
     got = _run(ctx, w, 1)
     _same(got, exp, "growth")
+    assert got[1]["link_chain"] == 3 and exp[1]["link_chain"] == 3
     monkeypatch.setenv("ISX_LINK_TEST_CAPS", "1000000000,4")
     got = _run(ctx, w, 1)
     _same(got, exp, "row growth only")
+    assert got[1]["link_chain"] == 3
 
 
 def test_bucket_chain_vs_oracle_multi_split(ctx):
@@ -104,7 +110,7 @@ def test_bucket_chain_vs_oracle_multi_split(ctx):
             exp[k].append(o[k])
     exp = {k: np.concatenate(v) for k, v in exp.items()}
     util.assert_same(util.canon_from_struct(got), util.canon_from_struct(exp), float_tol=1e-6, what="multi-split")
-    assert s["n_ld"] > 100
+    assert s["n_ld"] > 100 and s["link_chain"] == 3
 
 
 def test_sparse_pair_ids_take_the_hashed_chains(ctx, monkeypatch):
@@ -118,6 +124,7 @@ def test_sparse_pair_ids_take_the_hashed_chains(ctx, monkeypatch):
     monkeypatch.setenv("ISX_LINK_CHAIN", "sorted")
     exp = _run(ctx, w, 1)
     _same(got, exp, "hashed chains")
+    assert got[1]["link_chain"] == 3 and exp[1]["link_chain"] == 1
     assert exp[1]["n_ld"] > 100
 
 
@@ -127,9 +134,10 @@ def test_batch_without_sites_or_pairs(ctx):
     w = synth.make_workload(genome_len=30_000, coverage=30, n_sites=0, err=0.0, seed=8, skip_mm=True)
     f, s = _run(ctx, w, 1)
     assert s["n_ld"] == 0 and s["n_edges"] == 0 and len(f["ld"]) == 0
+    assert s["link_chain"] == 0                 # no SNP site: no chain is entered
     w = synth.make_workload(genome_len=200_000, coverage=40, n_sites=20, err=0.0, seed=8, skip_mm=True, af_lo=0.3, af_hi=0.5)
     f, s = _run(ctx, w, 1)
-    assert s["n_sites"] >= 15 and s["n_ld"] <= 2
+    assert s["n_sites"] >= 15 and s["n_ld"] <= 2 and s["link_chain"] == 3
 
 
 @pytest.mark.parametrize("cov,sites,glen", [(60, 1500, 200_000), (150, 2600, 4096)])
@@ -145,6 +153,8 @@ def test_mm_site_table_in_position_order_without_a_sort(ctx, monkeypatch, cov, s
     monkeypatch.setenv("ISX_LINK_SITE_SORT", "rocprim")
     exp = _run(ctx, w, M)
     _same(got, exp, "window table vs sort")
+    # (the second case's sites are so dense that one of them has more than 768 unique (site2, mm, combo) keys: it falls back by itself)
+    assert got[1]["link_chain"] == exp[1]["link_chain"] == (3 if glen > 4096 else 1)
     assert exp[1]["n_ld"] > 500 and exp[1]["n_sites"] > 0.5 * sites
     e = got[0]["entries"] if "entries" in got[0] else None
     assert e is None or e.tobytes() == exp[0]["entries"].tobytes()
