@@ -507,6 +507,51 @@ int isx_cmpset_compare(isx_cmpset *set, double min_freq, int64_t cap_rows, isx_c
 int isx_cmpset_pair_snps(isx_cmpset *set, int32_t i, int32_t j, int64_t *n_rows);
 int isx_cmpset_fetch_snps(isx_cmpset *set, isx_compare_snp *rows);
 
+/* ---- SNV pooling across the set (`inStrain compare --bams`: polymorpher.py:39-142 PoolController, :318-571) ----
+ * The sites of a scaffold are the union of the samples' own SNV positions; every sample that has the scaffold brings A C T G for every
+ * site: its own row's counts where it owns the site, the all-level counts of its reads elsewhere (get_pooling_counts, :313-316).
+ *   own row      the highest-mm row of a position among the rows that are NOT cryptic (:65-68)
+ *   has          some level of the sample is present on the scaffold (the rule of isx_cmpset_compare)
+ *   pooled       at least two samples have the scaffold (compare_controller.py:484); other scaffolds have no site
+ * Order of calls: isx_cmpset_pool_enable, every isx_cmpset_add, isx_cmpset_pool_sites, isx_cmpset_pool_add for every batch again (the
+ * "pull from the BAM"), isx_cmpset_pool_summary / isx_cmpset_pool_fetch_sample.  The samples share one reference (ref_base of a site is
+ * taken from an own row).  A site without a sample at >= 5 reads, on which the reference raises (:524-529 inner join, then the int
+ * cast), is reported with n_detect_5x = 0.  Integers only: two calls give identical bytes.
+ * Device memory: 17 bytes x sites x samples + one bit per set position. */
+typedef struct {
+    uint32_t gpos;              /* set position */
+    uint32_t n_detect;          /* sample_detections: samples with any count > 0 */
+    uint64_t cnt[4];            /* A C T G summed over the samples that have the scaffold; depth = their sum */
+    uint32_t n_detect_5x;       /* sample_5x_detections: samples with A + C + T + G >= 5 */
+    uint16_t cls_count[5];      /* own rows of class DivergentSite, SNS, SNV, con_SNV, pop_SNV (AmbiguousReference counts nowhere) */
+    uint8_t ref_base;           /* 0..4 */
+    uint8_t con_base;           /* argmax of cnt, ties to the lowest of A C T G (calc_con_base) */
+    uint8_t var_base;           /* first index of the maximum after zeroing con_base (calc_var_base) */
+    uint8_t n_con_bases;        /* distinct con_base values of the own rows ... */
+    uint8_t con_bases;          /* ... in order of first appearance over the samples, 2 bits each from bit 0 */
+    uint8_t pad[5];
+} isx_pool_site;                /* 64 bytes */
+
+/* before the first isx_cmpset_add (after it: ISX_ERR_STATE): isx_cmpset_add also keeps every sample's own rows (24 bytes each) */
+int isx_cmpset_pool_enable(isx_cmpset *set);
+/* after the last add: the site list, every sample's own rows scattered into its counts / meta columns.  *n_sites = sites of the set.
+ * A later isx_cmpset_add discards all of it. */
+int isx_cmpset_pool_sites(isx_cmpset *set, int64_t *n_sites);
+int isx_cmpset_pool_fetch_sites(isx_cmpset *set, uint32_t *gpos);       /* [n_sites] ascending set positions */
+/* The all-level counts of `batch` at the sites of its scaffolds that the sample has and does not own; arguments and host-side checks as
+ * for isx_cmpset_add, all made before anything is launched.  A batch with a count table (one level) is read at the sites; one with an
+ * entry table (mm profiling on) is walked entry by entry.  A one-level pipe slot without a count table (isx_pipe_params.want_counts = 0)
+ * or a lean slot: ISX_ERR_STATE.  Scaffolds the set does not name, the sample does not have or that are not pooled are skipped; the same
+ * (sample, scaffold) twice, or a call before isx_cmpset_pool_sites: ISX_ERR_STATE. */
+int isx_cmpset_pool_add(isx_cmpset *set, int32_t sample, isx_batch *batch, int32_t n_batch_scaffolds, const int64_t *batch_scaffold_bounds,
+                        const int32_t *set_scaffold_ids);
+/* PMdb (polymorpher.py:471-551): one row per site, cap_sites >= n_sites.  ISX_ERR_STATE (naming the first one) when a (sample,
+ * scaffold) with sites still to pull was never handed to isx_cmpset_pool_add. */
+int isx_cmpset_pool_summary(isx_cmpset *set, int64_t cap_sites, isx_pool_site *out, float *device_ms);
+/* DSTdb columns of one sample (polymorpher.py:397-448): counts[n_sites][4] A C T G; meta[n_sites]: bit 0 the sample has the site's
+ * scaffold (a row of DSTdb), bit 1 it owns the site, bits 2..4 the own row's class, bits 5..6 its con_base */
+int isx_cmpset_pool_fetch_sample(isx_cmpset *set, int32_t sample, uint32_t *counts, uint8_t *meta);
+
 /* ---- gene profiling (GeneProfile.py:304-707 profile_genes_from_profile: `inStrain profile -g genes.fna`) ----
  * A gene set lives on the device for as long as the caller keeps it: coordinates + the genes' own letters (upper-case
  * A/C/G/T/N as in the .fna, gene orientation), uploaded once.  Genes of one scaffold are consecutive in the set.

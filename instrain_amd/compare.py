@@ -48,6 +48,7 @@ def calc_mm2overlap(batch1, batch2, scaffold_bounds, min_cov=5):
 
 
 BASES = np.array(["A", "C", "T", "G", "N"])
+POOL_CLASSES = ("DivergentSite", "SNS", "SNV", "con_SNV", "pop_SNV")        # the <class>_count columns of PMdb (polymorpher.py:492)
 
 
 def compare_scaffolds(batch1, batch2, scaffold_bounds, scaffold_names=None, name1="sample1", name2="sample2",
@@ -134,8 +135,12 @@ class SampleSet:
     """The samples of one `inStrain compare` run on the device.  scaffold_names / scaffold_lengths: the scaffolds to compare, in the
     order of the output.  Samples are numbered in the order of their first add_batch."""
 
-    def __init__(self, ctx, scaffold_names, scaffold_lengths, min_cov=5):
+    def __init__(self, ctx, scaffold_names, scaffold_lengths, min_cov=5, pooling=False):
+        """pooling: also keep every sample's own SNV rows for pool_sites() / pool_add() / pooled_tables() (`compare --bams`)"""
         self.ctx, self.lib = ctx, ctx.lib
+        self.pooling = bool(pooling)
+        self.n_pool_sites = None                                # sites of the last pool_sites(); None: none since the last add_batch
+        self.pool_device_ms, self.pool_raw = 0.0, None
         self.names = list(scaffold_names)
         self.lengths = np.ascontiguousarray(scaffold_lengths, dtype=np.int64)
         if len(self.names) != len(self.lengths) or len(set(self.names)) != len(self.names):
@@ -149,6 +154,8 @@ class SampleSet:
         check(self.lib.isx_cmpset_create(ctx.h, len(self.names), self.lengths.ctypes.data, int(min_cov), C.byref(h)))
         self.h = h
         ctx._adopt(self)
+        if self.pooling:
+            check(self.lib.isx_cmpset_pool_enable(self.h))
 
     def add_batch(self, sample_name, batch, batch_scaffold_names, batch_bounds, mm_values=None):
         """what `batch` (a run Batch or a collected pipe slot) holds of the sample; scaffolds the set does not name are skipped.
@@ -166,6 +173,7 @@ class SampleSet:
                                       bb.ctypes.data, ids.ctypes.data, None if mmv is None else mmv.ctypes.data))
         if not known:                                           # (a refused batch leaves the set as it was)
             self.samples.append(sample_name)
+        self.n_pool_sites = None                                # (the library has dropped its pooling state)
 
     def compare(self, min_freq=0.05, logs=None):
         """-> the comparisonsTable rows (the columns of compare_scaffolds) of every pair of samples over every scaffold both have,
@@ -221,6 +229,79 @@ class SampleSet:
             ok = ~np.isin(scaf, sorted(self.failed))
             raw, scaf = raw[ok], scaf[ok]
         return {"raw": raw, "scaffold": scaf, "position": raw["gpos"].astype(np.int64) - self.offsets[scaf]}
+
+    # ---- SNV pooling (polymorpher.py PoolController; include/instrain_amd.h isx_cmpset_pool_*) ----
+    def pool_sites(self):
+        """after the last add_batch: the union of the samples' own SNV positions on every scaffold at least two samples have -> number
+        of sites.  Every batch then goes through pool_add() once more (the reference goes back to the BAM)."""
+        n = C.c_int64(0)
+        check(self.lib.isx_cmpset_pool_sites(self.h, C.byref(n)))
+        self.n_pool_sites = n.value
+        return n.value
+
+    def pool_site_positions(self):
+        """the sites of the last pool_sites() as ascending set positions"""
+        raw = np.zeros(self.n_pool_sites or 0, dtype=np.uint32)
+        check(self.lib.isx_cmpset_pool_fetch_sites(self.h, raw.ctypes.data))
+        return raw
+
+    def pool_add(self, sample_name, batch, batch_scaffold_names, batch_bounds):
+        """the all-level base counts of `batch` at the sites the sample does not own (get_pooling_counts); arguments as add_batch.  A
+        one-level pipe slot needs the pipe's want_counts.  The batch may be closed / its slot released as soon as this returns."""
+        bb = np.ascontiguousarray(batch_bounds, dtype=np.int64)
+        ids = np.array([self.index.get(n, -1) for n in batch_scaffold_names], dtype=np.int32)
+        if len(bb) != len(ids) + 1:
+            raise ValueError("pool_add: batch_bounds has one entry more than the batch has scaffolds")
+        if sample_name not in self.samples:
+            raise ValueError("pool_add: sample %r was never added" % (sample_name,))
+        check(self.lib.isx_cmpset_pool_add(self.h, self.samples.index(sample_name), batch.h, len(ids), bb.ctypes.data, ids.ctypes.data))
+
+    def pooled_tables(self):
+        """-> (DSTdb, PMdb) of polymorpher.py:397-448 / :471-551 as pandas frames.  DSTdb: index (sample, position), columns A C T G and
+        the categorical `scaffold`, rows by (scaffold in set order, sample in insertion order, position).  PMdb: index position, the
+        reference's columns.  A site no sample sees at >= 5 reads (the reference raises there) has sample_5x_detections 0."""
+        import pandas as pd
+        n_s, n_a = C.c_int32(0), C.c_int32(0)
+        check(self.lib.isx_cmpset_axis(self.h, C.byref(n_s), C.byref(n_a), None))
+        S = n_s.value
+        n = self.n_pool_sites or 0                              # (None: the library refuses the call below)
+        summary = np.zeros(n, dtype=_lib.POOL_SITE_DT)
+        ms = C.c_float(0)
+        check(self.lib.isx_cmpset_pool_summary(self.h, n, summary.ctypes.data, C.byref(ms)))
+        self.pool_device_ms = ms.value
+        counts, meta = np.zeros((S, n, 4), dtype=np.uint32), np.zeros((S, n), dtype=np.uint8)
+        for i in range(S):
+            check(self.lib.isx_cmpset_pool_fetch_sample(self.h, i, counts[i].ctypes.data, meta[i].ctypes.data))
+        self.pool_raw = {"summary": summary, "counts": counts, "meta": meta}
+        gpos = summary["gpos"].astype(np.int64)
+        scaf = np.searchsorted(self.offsets, gpos, side="right") - 1
+        position = gpos - self.offsets[scaf]
+        cats = pd.CategoricalDtype([self.names[i] for i in np.unique(scaf)])
+        names = np.array(self.names, dtype=object)
+        # DSTdb: one row per (sample that has the scaffold, site)
+        si, ri = np.nonzero(meta & _lib.POOL_META_HAS)
+        order = np.lexsort((ri, si, scaf[ri]))
+        si, ri = si[order], ri[order]
+        c = counts[si, ri].astype(np.int64)
+        dst = pd.DataFrame({"A": c[:, 0], "C": c[:, 1], "T": c[:, 2], "G": c[:, 3]},
+                           index=pd.MultiIndex.from_arrays([np.array(self.samples, dtype=object)[si], position[ri]]))
+        dst["scaffold"] = pd.Categorical(names[scaf[ri]], dtype=cats)
+        # PMdb
+        tot = summary["cnt"].astype(np.int64)
+        key = summary["n_con_bases"].astype(np.int64) * 256 + summary["con_bases"]
+        text = {k: str(np.array(["ACTG"[(k & 255) >> (2 * j) & 3] for j in range(k >> 8)], dtype=object)) for k in np.unique(key).tolist()}
+        pm = pd.DataFrame({"A": tot[:, 0], "C": tot[:, 1], "T": tot[:, 2], "G": tot[:, 3]}, index=position)
+        pm["scaffold"] = pd.Categorical(names[scaf], dtype=cats)
+        pm["depth"] = tot.sum(axis=1)
+        pm["ref_base"] = BASES[np.minimum(summary["ref_base"], 4)]
+        pm["sample_5x_detections"] = summary["n_detect_5x"].astype(np.int64)
+        pm["sample_detections"] = summary["n_detect"].astype(np.int64)
+        for j, cls in enumerate(POOL_CLASSES):
+            pm[cls + "_count"] = summary["cls_count"][:, j].astype(np.int64)
+        pm["sample_con_bases"] = pd.Series(key, index=pm.index).map(text).astype(object) if n else np.zeros(0, dtype=object)
+        pm["con_base"] = BASES[summary["con_base"]]
+        pm["var_base"] = BASES[summary["var_base"]]
+        return dst, pm
 
     def close(self):
         if self.h:
@@ -278,3 +359,43 @@ def genome_wide(table, stb, bin2length=None, mm_level=False):
     if not mm_level:
         del db["mm"]
     return db
+
+
+# ---- the user tables of SNV pooling (SNVprofile.py:367-410) ----
+POOLED_SNV_INFO_COLUMNS = ["scaffold", "position", "depth", "A", "C", "T", "G", "ref_base", "con_base", "var_base", "sample_detections",
+                           "sample_5x_detections", "DivergentSite_count", "SNS_count", "SNV_count", "con_SNV_count", "pop_SNV_count"]
+
+
+def pooled_SNV_info(PMdb):
+    """pooled_SNV_info (SNVprofile.py:367-375): PMdb with `position` as a column, the reference's column order, whatever else PMdb
+    holds (sample_con_bases) behind it"""
+    db = PMdb.copy()
+    db["position"] = db.index
+    db = db.reset_index(drop=True)
+    if len(db) == 0:
+        return db
+    return db[[c for c in POOLED_SNV_INFO_COLUMNS if c in db.columns] + [c for c in db.columns if c not in POOLED_SNV_INFO_COLUMNS]]
+
+
+def pooled_SNV_data(DSTdb, samples=None):
+    """pooled_SNV_data and pooled_SNV_data_keys (SNVprofile.py:377-410) -> (data: sample, scaffold, position, A, C, T, G with samples and
+    scaffolds as integer keys; keys: key, sample, scaffold with NaN where a key names only one of them).  The reference numbers both by
+    enumerating a set(); here scaffolds are numbered in category order (the set's) and samples in the order of `samples` (a
+    SampleSet's .samples), None = DSTdb's order of first appearance."""
+    import pandas as pd
+    level0 = DSTdb.index.get_level_values(0)
+    if samples is None:
+        sample_codes, samples = pd.factorize(level0, sort=False)
+    else:
+        samples = [s for s in samples if s in set(level0)]
+        sample_codes = pd.Index(samples).get_indexer(level0)
+    scaffolds = list(DSTdb["scaffold"].cat.categories)
+    data = pd.DataFrame({"sample": sample_codes.astype(np.int64), "scaffold": DSTdb["scaffold"].cat.codes.to_numpy().astype(np.int64),
+                         "position": DSTdb.index.get_level_values(1).to_numpy().astype(np.int64)})
+    for c in "ACTG":
+        data[c] = DSTdb[c].to_numpy()
+    n = max(len(samples), len(scaffolds))
+    keys = pd.DataFrame({"key": np.arange(n),
+                         "sample": [samples[i] if i < len(samples) else np.nan for i in range(n)],
+                         "scaffold": [scaffolds[i] if i < len(scaffolds) else np.nan for i in range(n)]})
+    return data, keys

@@ -10,6 +10,7 @@
 //   planes[level][word]   one bit per set position: coverage cumulated over levels <= level reaches min_cov
 //   present[scaffold][level]   the level is a key of the sample's covT on the scaffold (Acc.present of run_compare)
 //   rows[]                the highest-mm SNV row of every position, in set-position order
+//   prows[]               (after isx_cmpset_pool_enable) the highest-mm row that is not cryptic: SNV pooling, isx_compare_pool.hip
 // so a batch can go as soon as it has been added.  The set's position space starts every scaffold on a 64-position word
 // (cmpset_layout.cpp): no word belongs to two scaffolds, `both` of a pair is popcount(a & b) word by word.
 // Everything counted here is an integer; sums go through 64-bit integer atomics, so a call's bytes do not depend on timing.
@@ -19,20 +20,11 @@
 #include <vector>
 #include <rocprim/rocprim.hpp>
 
-#include "isx_batch.h"
+#include "isx_compare_set.h"
+
+using namespace isxset;
 
 namespace {
-
-struct CsRow {                          // what the SNP half reads of an isx_snv
-    uint32_t gpos;                      // set position
-    uint8_t con_base, ref_base, var_base, allele_count;
-    uint32_t cnt[4];
-};
-
-struct PackJob {                        // one batch scaffold that the set names: its words as a run of the call's job words
-    int64_t jw0;                        // first job word (ascending; a sentinel entry closes the list)
-    int64_t dst_w0, src0, len;          // first word in the set, first position in the batch, positions
-};
 
 struct CovItem { uint16_t ra, rb; uint32_t out; };      // two staged rows and the output row their count goes to (ra == rb: one sample's own count)
 
@@ -61,16 +53,6 @@ __global__ void __launch_bounds__(256) k_pack_plane(const uint32_t *cov, uint32_
     const unsigned long long mask = __ballot(bit);
     const int64_t dw = j.dst_w0 + (jw - j.jw0);
     if (lane == 0 && dw >= 0 && dw < n_words) plane[dw] = mask;
-}
-
-__device__ __forceinline__ int seg_of(const int64_t *bounds, int n_seg, int64_t g)
-{
-    int lo = 0, hi = n_seg;             // bounds[lo] <= g < bounds[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (bounds[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // (set position, mm) keys of a batch's SNV rows; rows of scaffolds the set does not name get the all-ones key (sorted last)
@@ -110,13 +92,44 @@ __global__ void k_gather_last(const uint64_t *keys, const uint32_t *idx, const u
     out[pos[i]] = r;
 }
 
-__global__ void k_row_keys(const CsRow *rows, uint32_t n, uint32_t *keys, uint32_t *idx)
+// the pooling keys (polymorpher.py:65-68): the same, with cryptic rows keyed out as well
+__global__ void k_pool_keys(const isx_snv *snv, uint32_t n, const int64_t *bbounds, int n_bscaf, const int64_t *set_pos0, uint64_t *keys,
+                            uint32_t *idx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = snv[i].gpos;
+    const int sc = seg_of(bbounds, n_bscaf, g);
+    const int64_t p0 = set_pos0[sc];
+    const bool in = p0 >= 0 && g >= bbounds[sc] && g < bbounds[sc + 1] && !snv[i].cryptic;
+    keys[i] = in ? ((uint64_t)(p0 + (g - bbounds[sc])) << 16) | snv[i].mm : ~0ull;
+    idx[i] = i;
+}
+
+__global__ void k_gather_pool(const uint64_t *keys, const uint32_t *idx, const uint32_t *flags, const uint32_t *pos, uint32_t n,
+                              const isx_snv *snv, PoolRow *out, uint32_t cap, uint32_t *total)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i + 1 == n) total[0] = pos[i] + flags[i];
+    if (!flags[i] || pos[i] >= cap) return;
+    const isx_snv x = snv[idx[i]];
+    PoolRow r;
+    r.gpos = (uint32_t)(keys[i] >> 16);
+    r.con_base = x.con_base; r.ref_base = x.ref_base; r.cls = x.cls; r.pad = 0;
+    for (int k = 0; k < 4; k++) r.cnt[k] = x.cnt[k];
+    out[pos[i]] = r;
+}
+
+template <class Row>
+__global__ void k_row_keys(const Row *rows, uint32_t n, uint32_t *keys, uint32_t *idx)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { keys[i] = rows[i].gpos; idx[i] = i; }
 }
 
-__global__ void k_gather_rows(const CsRow *rows, const uint32_t *idx, uint32_t n, CsRow *out)
+template <class Row>
+__global__ void k_gather_rows(const Row *rows, const uint32_t *idx, uint32_t n, Row *out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && idx[i] < n) out[i] = rows[idx[i]];
@@ -283,77 +296,21 @@ __global__ void __launch_bounds__(256) k_cmpset_snp(const SnpArgs a)
     }
 }
 
-struct Sample {
-    std::vector<int32_t> mm;            // real mm of every own level (fixed by the first batch)
-    uint64_t *planes = nullptr;         // [levels][n_words]
-    std::vector<uint8_t> have;          // [n_scaf] the scaffold has been added
-    std::vector<uint8_t> present;       // [n_scaf][levels]
-    CsRow *rows = nullptr;
-    size_t n_rows = 0, cap_rows = 0;
-    bool sorted = true;                 // rows ascend (every batch so far brought higher scaffolds than the ones before)
-    int32_t max_sid = -1;
-};
-
-template <class T>
-struct SetBuf {                         // a device array that lives as long as its owner says
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t fit(size_t n)
-    {
-        if (p && cap >= n) return hipSuccess;
-        drop();
-        const hipError_t e = isx_raw_dev_malloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = std::max<size_t>(n, 1);
-        return e;
-    }
-    hipError_t put(const std::vector<T> &h, hipStream_t s)
-    {
-        hipError_t e = fit(h.size());
-        if (e == hipSuccess && !h.empty()) e = hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
-        return e;
-    }
-    void drop() { if (p) isx_dev_free(p); p = nullptr; cap = 0; }
-};
-
 }  // namespace
 
-struct isx_cmpset {
-    isx_ctx *ctx = nullptr;
-    int32_t min_cov = 5, n_scaf = 0;
-    std::vector<int64_t> len, woff, spos;   // lengths; first word of every scaffold + total; the same in positions
-    int64_t n_words = 0;
-    std::vector<Sample> samples;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // scratch of isx_cmpset_add
-    SetBuf<uint32_t> cov, present, idx, idx_in, flags, pos;
-    SetBuf<float> scratch_f;
-    SetBuf<int64_t> bbounds, set_pos0;
-    SetBuf<uint8_t> acc, temp;
-    SetBuf<PackJob> jobs;
-    SetBuf<uint64_t> keys, keys_in;
-    // what the last isx_cmpset_compare left for isx_cmpset_pair_snps
-    bool compared = false;
-    double min_freq = 0.05;
-    int32_t A = 0;
-    SetBuf<const uint64_t *> d_planes;
-    SetBuf<const CsRow *> d_rows;
-    SetBuf<uint32_t> d_n_rows, d_failed, d_cursor;
-    SetBuf<int16_t> d_lmap;
-    SetBuf<uint8_t> d_pres;
-    SetBuf<int64_t> d_spos;
-    SetBuf<int32_t> d_axis;
-    SetBuf<unsigned long long> d_cnt, d_snp;
-    SetBuf<isx_compare_snp> snp_rows;
-    uint32_t n_snp_rows = 0;
-};
+namespace isxset {
 
-namespace {
-
-int grow_temp(isx_cmpset *st, size_t bytes)
+int cmpset_grow_temp(isx_cmpset *st, size_t bytes)
 {
     if (st->temp.cap < bytes + 256) HIP_TRY(st->temp.fit(bytes + 256));
     return ISX_OK;
 }
+
+}  // namespace isxset
+
+namespace {
+
+int grow_temp(isx_cmpset *st, size_t bytes) { return cmpset_grow_temp(st, bytes); }
 
 // the sample's real mm values and the set's level axis
 int level_axis(const isx_cmpset *st, std::vector<int32_t> &axis, int32_t *n_axis, std::vector<int32_t> &map)
@@ -369,17 +326,18 @@ int level_axis(const isx_cmpset *st, std::vector<int32_t> &axis, int32_t *n_axis
     return isx_cmpset_level_map(S, n_levels.data(), all.data(), ISX_CMPSET_MAX_LEVELS, axis.data(), n_axis, map.data());
 }
 
-// rows of a sample whose batches did not arrive in set order: one sort by position
-int sort_rows(isx_cmpset *st, Sample &sm)
+// rows (compare rows or pool rows) of a sample whose batches did not arrive in set order: one sort by position
+template <class Row>
+int sort_rows_of(isx_cmpset *st, Row *&rows, size_t n_rows, size_t cap_rows, bool &sorted)
 {
-    if (sm.sorted || sm.n_rows < 2) { sm.sorted = true; return ISX_OK; }
+    if (sorted || n_rows < 2) { sorted = true; return ISX_OK; }
     hipStream_t s = st->ctx->stream;
-    const uint32_t n = (uint32_t)sm.n_rows;
+    const uint32_t n = (uint32_t)n_rows;
     SetBuf<uint32_t> k_in, k_out;
-    CsRow *fresh = nullptr;
+    Row *fresh = nullptr;
     auto done = [&](int rc) { k_in.drop(); k_out.drop(); if (fresh) isx_dev_free(fresh); return rc; };
     if (k_in.fit(n) != hipSuccess || k_out.fit(n) != hipSuccess || st->idx_in.fit(n) != hipSuccess || st->idx.fit(n) != hipSuccess ||
-        isx_raw_dev_malloc(&fresh, sm.cap_rows * sizeof(CsRow)) != hipSuccess) {
+        isx_raw_dev_malloc(&fresh, cap_rows * sizeof(Row)) != hipSuccess) {
         isx_set_error("isx_cmpset_compare: out of device memory while ordering a sample's SNV rows");
         return done(ISX_ERR_HIP);
     }
@@ -388,22 +346,47 @@ int sort_rows(isx_cmpset *st, Sample &sm)
     int rc = grow_temp(st, tb);
     if (rc) return done(rc);
     const dim3 blk(256), grid((n + 255) / 256);
-    hipLaunchKernelGGL(k_row_keys, grid, blk, 0, s, sm.rows, n, k_in.p, st->idx_in.p);
+    hipLaunchKernelGGL(k_row_keys<Row>, grid, blk, 0, s, rows, n, k_in.p, st->idx_in.p);
     tb = st->temp.cap;
     if (rocprim::radix_sort_pairs(st->temp.p, tb, k_in.p, k_out.p, st->idx_in.p, st->idx.p, n, 0, 32, s) != hipSuccess) {
         isx_set_error("isx_cmpset_compare: radix sort of a sample's SNV rows failed");
         return done(ISX_ERR_HIP);
     }
-    hipLaunchKernelGGL(k_gather_rows, grid, blk, 0, s, sm.rows, st->idx.p, n, fresh);
+    hipLaunchKernelGGL(k_gather_rows<Row>, grid, blk, 0, s, rows, st->idx.p, n, fresh);
     if (isx_wait_stream(s) != hipSuccess) { isx_set_error("isx_cmpset_compare: ordering a sample's SNV rows failed"); return done(ISX_ERR_HIP); }
-    std::swap(sm.rows, fresh);
-    sm.sorted = true;
+    std::swap(rows, fresh);
+    sorted = true;
     return done(ISX_OK);
 }
+
+int sort_rows(isx_cmpset *st, Sample &sm) { return sort_rows_of(st, sm.rows, sm.n_rows, sm.cap_rows, sm.sorted); }
 
 int pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 }  // namespace
+
+namespace isxset {
+
+int cmpset_sort_pool_rows(isx_cmpset *st, Sample &sm) { return sort_rows_of(st, sm.prows, sm.n_prows, sm.cap_prows, sm.psorted); }
+
+int cmpset_check_batch(const char *who, const isx_cmpset *st, int32_t sample, const isx_batch *b, int32_t n_bscaf, const int64_t *bb,
+                       const int32_t *ids)
+{
+    const std::string w(who);
+    if (!st || !b || !bb || !ids || n_bscaf <= 0 || sample < 0 || sample >= ISX_CMPSET_MAX_SAMPLES) {
+        isx_set_error(w + ": bad argument");
+        return ISX_ERR_ARG;
+    }
+    if (!b->ran) { isx_set_error(w + ": run the batch first"); return ISX_ERR_STATE; }
+    if (b->ctx != st->ctx) { isx_set_error(w + ": the batch belongs to another ctx than the set"); return ISX_ERR_ARG; }
+    if (bb[0] != 0 || bb[n_bscaf] != b->n_pos) { isx_set_error(w + ": batch_scaffold_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
+    for (int i = 0; i < n_bscaf; i++)
+        if (bb[i + 1] <= bb[i]) { isx_set_error(w + ": batch_scaffold_bounds must be strictly ascending"); return ISX_ERR_ARG; }
+    if (b->n_pos > (int64_t)0xFFFFFFFFll) { isx_set_error(w + ": flat space beyond 2^32 positions"); return ISX_ERR_ARG; }
+    return ISX_OK;
+}
+
+}  // namespace isxset
 
 extern "C" {
 
@@ -440,7 +423,9 @@ void isx_cmpset_destroy(isx_cmpset *st)
     for (Sample &s : st->samples) {
         if (s.planes) isx_dev_free(s.planes);
         if (s.rows) isx_dev_free(s.rows);
+        if (s.prows) isx_dev_free(s.prows);
     }
+    cmpset_pool_drop(st);
     st->cov.drop(); st->present.drop(); st->idx.drop(); st->idx_in.drop(); st->flags.drop(); st->pos.drop(); st->scratch_f.drop();
     st->bbounds.drop(); st->set_pos0.drop(); st->acc.drop(); st->temp.drop(); st->jobs.drop(); st->keys.drop(); st->keys_in.drop();
     st->d_planes.drop(); st->d_rows.drop(); st->d_n_rows.drop(); st->d_failed.drop(); st->d_cursor.drop(); st->d_lmap.drop();
@@ -452,16 +437,8 @@ void isx_cmpset_destroy(isx_cmpset *st)
 int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf, const int64_t *bb, const int32_t *ids,
                    const int32_t *level_mm_values)
 {
-    if (!st || !b || !bb || !ids || n_bscaf <= 0 || sample < 0 || sample >= ISX_CMPSET_MAX_SAMPLES) {
-        isx_set_error("isx_cmpset_add: bad argument");
-        return ISX_ERR_ARG;
-    }
-    if (!b->ran) { isx_set_error("isx_cmpset_add: run the batch first"); return ISX_ERR_STATE; }
-    if (b->ctx != st->ctx) { isx_set_error("isx_cmpset_add: the batch belongs to another ctx than the set"); return ISX_ERR_ARG; }
-    if (bb[0] != 0 || bb[n_bscaf] != b->n_pos) { isx_set_error("isx_cmpset_add: batch_scaffold_bounds must span [0, n_pos]"); return ISX_ERR_ARG; }
-    for (int i = 0; i < n_bscaf; i++)
-        if (bb[i + 1] <= bb[i]) { isx_set_error("isx_cmpset_add: batch_scaffold_bounds must be strictly ascending"); return ISX_ERR_ARG; }
-    if (b->n_pos > (int64_t)0xFFFFFFFFll) { isx_set_error("isx_cmpset_add: flat space beyond 2^32 positions"); return ISX_ERR_ARG; }
+    const int rc_args = cmpset_check_batch("isx_cmpset_add", st, sample, b, n_bscaf, bb, ids);
+    if (rc_args) return rc_args;
     if (b->lean && !b->d_counts) { isx_set_error("a batch of a lean pipe slot (isx_pipe_params.lean_output) keeps no dense coverage / clonality arrays"); return ISX_ERR_STATE; }
     const int M = b->M;
     if (M <= 0 || M > ISX_CMPSET_MAX_LEVELS) {
@@ -522,6 +499,7 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
         sm.present.assign((size_t)st->n_scaf * M, 0);
     }
     st->compared = false;
+    st->pooled = false;                             // the sites, ranks and pulled counts of isx_cmpset_pool_sites are of the set as it was
     // scratch, all sized before anything is launched
     HIP_TRY(st->cov.fit(n_pos)); HIP_TRY(st->scratch_f.fit((size_t)n_pos * 2));
     HIP_TRY(st->acc.fit(level_acc_bytes(n_bscaf))); HIP_TRY(st->present.fit((size_t)n_bscaf * M));
@@ -545,6 +523,15 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
             HIP_TRY(isx_wait_stream(s));
             if (sm.rows) isx_dev_free(sm.rows);
             sm.rows = grown; sm.cap_rows = want;
+        }
+        if (st->pool_on && sm.cap_prows < sm.n_prows + n_snv) {
+            const size_t want = std::max(sm.n_prows + n_snv, sm.cap_prows * 2);
+            PoolRow *grown = nullptr;
+            HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(PoolRow)));
+            if (sm.n_prows) HIP_TRY(hipMemcpyAsync(grown, sm.prows, sm.n_prows * sizeof(PoolRow), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(isx_wait_stream(s));
+            if (sm.prows) isx_dev_free(sm.prows);
+            sm.prows = grown; sm.cap_prows = want;
         }
     }
     SummaryIn in{};
@@ -575,6 +562,20 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
                            sm.rows + sm.n_rows, (uint32_t)(sm.cap_rows - sm.n_rows), st->pos.p + n_snv);
         HIP_TRY(hipMemcpyAsync(&n_new, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
     }
+    // pool rows: the same scheme on keys that leave the cryptic rows out, so a position's last row is its highest-mm row that counts
+    uint32_t n_new_pool = 0;
+    if (n_snv && st->pool_on) {
+        const dim3 grid((n_snv + 255) / 256);
+        hipLaunchKernelGGL(k_pool_keys, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
+        size_t tb = st->temp.cap;
+        HIP_TRY(rocprim::radix_sort_pairs(st->temp.p, tb, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
+        hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
+        tb = st->temp.cap;
+        HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
+        hipLaunchKernelGGL(k_gather_pool, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, b->d_snv,
+                           sm.prows + sm.n_prows, (uint32_t)(sm.cap_prows - sm.n_prows), st->pos.p + n_snv);
+        HIP_TRY(hipMemcpyAsync(&n_new_pool, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(isx_wait_stream(s));
     HIP_TRY(hipGetLastError());
     // only now is the batch part of the sample
@@ -586,6 +587,8 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     }
     if (n_new && sm.n_rows && min_sid < sm.max_sid) sm.sorted = false;
     sm.n_rows += std::min<size_t>(n_new, sm.cap_rows - sm.n_rows);
+    if (n_new_pool && sm.n_prows && min_sid < sm.max_sid) sm.psorted = false;
+    sm.n_prows += std::min<size_t>(n_new_pool, sm.cap_prows - sm.n_prows);
     sm.max_sid = std::max(sm.max_sid, max_sid);
     return ISX_OK;
 }

@@ -851,14 +851,15 @@ def pipe_depth_of(opt, n_groups):
     return max(1, int((2 if n_groups > 1 else 1) if opt.pipe_depth is None else opt.pipe_depth))
 
 
-def open_pipe(ctx, opt, n_mm, depth, need):
-    """The read-level pipe of a run for batches of up to `need` = (positions, segments, splits); pipe.cap = what it was made with"""
+def open_pipe(ctx, opt, n_mm, depth, need, pool=False):
+    """The read-level pipe of a run for batches of up to `need` = (positions, segments, splits); pipe.cap = what it was made with.
+    pool: the run's slots are pulled for SNV pooling (SampleSet.pool_add), which reads a one-level slot's count table"""
     cap = (max(need[0], 1 << 16), max(need[1], 1 << 12), max(need[2], 64))
     pp = engine.Pipe(ctx, max_pos=cap[0], max_obs=0, max_segs=cap[1], max_splits=cap[2], depth=depth,
                      host_threads=opt.host_threads, pin_threads=False,
                      min_cov=opt.min_cov, min_freq=opt.min_freq, min_snp=opt.min_snp,
                      rarefied_coverage=opt.rarefied, n_mm_bins=n_mm,
-                     enable_linkage=True, seed=opt.seed, want_counts=opt.store_everything,
+                     enable_linkage=True, seed=opt.seed, want_counts=opt.store_everything or (pool and n_mm == 1),
                      # mm profiling on: the front end emits bit planes + the pairs' levels, the batches travel as 32-byte
                      # reference-delta records with the level in the header (round 6) -- half the bytes, the 14-ns stager
                      layout=int((_lib.LAYOUT_MM_DELTA_RECORDS if n_mm > 1 else 0) if opt.layout is None else opt.layout),
@@ -899,13 +900,14 @@ class _BatchRun:
 
     def __init__(self, bf, plan, refs, opt, make_pipe, depth, codes_of, est_segs, out, stage, bam=None, mm_values=None, mm_clamped=None,
                  gset=None, logs=None, scaffold_tables=None, scaffold_levels=None, genomes=None, compare_set=None, compare_sample=None,
-                 irep=None, irep_index=None):
+                 irep=None, irep_index=None, pool_set=None, pool_sample=None):
         self.bf, self.plan, self.refs, self.opt, self.make_pipe, self.depth = bf, plan, refs, opt, make_pipe, depth
         self.codes_of, self.est_segs, self.out, self.stage, self.bam = codes_of, est_segs, out, stage, bam
         self.mm_values, self.mm_clamped, self.gset, self.logs = mm_values, mm_clamped, gset, logs
         self.scaffold_tables, self.scaffold_levels = scaffold_tables, scaffold_levels
         self.genomes = genomes                       # genome_utilities.GenomeTables (profile_bam(stb=...)) or None
         self.compare_set, self.compare_sample = compare_set, compare_sample    # compare.SampleSet that gets every batch's sketch, or None
+        self.pool_set, self.pool_sample = pool_set, pool_sample    # compare.SampleSet (after pool_sites()) that pulls every batch's counts, or None
         self.irep, self.irep_index = irep, irep_index or {}    # engine.IRep of the run's genomes (scaffold name -> its index there), or None
         self.ekw = dict(opt.filter, skip_mm=opt.skip_mm, window_length=opt.window_length)
         self.pipe = self.cap = None
@@ -971,7 +973,7 @@ class _BatchRun:
                                       min_cov=opt.min_cov, started=g.t_submit, mm_clamped=self.mm_clamped, mm_values=self.mm_values)
             summaries = self.scaffold_tables is not None or self.scaffold_levels is not None or self.genomes is not None
             genes = self.gset is not None and bool(splits)
-            if summaries or genes or self.compare_set is not None:
+            if summaries or genes or self.compare_set is not None or self.pool_set is not None:
                 sb = np.r_[0, np.cumsum([self.refs[tid][1] for tid in g.tids])]
                 if summaries:
                     self.summarize(g, res["slot"], splits, sb)
@@ -979,6 +981,8 @@ class _BatchRun:
                     self.profile_genes(g, res["slot"], splits, sb)
                 if self.compare_set is not None:    # the slot's sketch (compare.SampleSet) before the slot goes back to the pipe
                     self.compare_set.add_batch(self.compare_sample, res["slot"], [self.plan[k][1] for k in g.items], sb, self.mm_values)
+                if self.pool_set is not None:       # the second pass of SNV pooling: the slot's counts at the sites the sample does not own
+                    self.pool_set.pool_add(self.pool_sample, res["slot"], [self.plan[k][1] for k in g.items], sb)
         finally:
             self.pipe.release(t)
             g.ticket = None
@@ -1126,6 +1130,9 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     unfiltered_raw_iRep, iRep_GC_corrected and unfiltered_iRep),
     `compare_set` (a compare.SampleSet on the same ctx) with `compare_sample` (this BAM's name in it, default: the path): every batch's
     sketch is added to the set before its slot is released (SampleSet.add_batch; without `compare_set` no such call is made),
+    `pool_set` (a compare.SampleSet(pooling=True) whose pool_sites() has run) with `pool_sample` (default: the path): the second pass of
+    SNV pooling -- every batch's slot is handed to SampleSet.pool_add before its release; a run with one mm bin then opens its pipe
+    with want_counts (without `pool_set` nothing changes),
     `batch_positions` / `batch_reads` (size of a device batch; `batch_observations` is accepted as 150 x batch_reads), `pipe_depth` (device batches in flight: the front end
     prepares batch k + 1 while batch k is profiled and its tables are cut), `stats` (dict that receives stage times).
     The BAM's reads go to the device as read segments (isx_pipe_submit_bam on a read-level pipe): the host never expands a
@@ -1185,11 +1192,14 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
             if i_names:
                 irep = engine.IRep(ctx, i_lengths, i_genome, len(genomes.genomes), mask_edges=genomes.mask_edges)
                 irep_index = {name: i for i, name in enumerate(i_names)}
-        run = _BatchRun(bf, plan, refs, opt, functools.partial(open_pipe, ctx, opt, n_mm, depth), depth, codes_of, est_segs, out, stage,
+        make_pipe = functools.partial(open_pipe, ctx, opt, n_mm, depth)
+        if kwargs.get('pool_set') is not None:
+            make_pipe = functools.partial(open_pipe, ctx, opt, n_mm, depth, pool=True)
+        run = _BatchRun(bf, plan, refs, opt, make_pipe, depth, codes_of, est_segs, out, stage,
                         bam=bam, mm_values=mm_values, mm_clamped=mm_clamped, gset=gset, logs=logs,
                         scaffold_tables=kwargs.get('scaffold_tables'), scaffold_levels=kwargs.get('scaffold_levels'), genomes=genomes,
                         compare_set=kwargs.get('compare_set'), compare_sample=kwargs.get('compare_sample', bam),
-                        irep=irep, irep_index=irep_index)
+                        irep=irep, irep_index=irep_index, pool_set=kwargs.get('pool_set'), pool_sample=kwargs.get('pool_sample', bam))
         # the pipe (pinned staging, device arena: tens of ms) is set up by one helper thread while another lays the groups out
         # (sequence codes, split tables: Python + numpy) -- a group's layout is then ready when the group before it is being handed
         # over (isx_pipe_submit_bam runs without the GIL)
