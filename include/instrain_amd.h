@@ -552,6 +552,55 @@ int isx_cmpset_pool_summary(isx_cmpset *set, int64_t cap_sites, isx_pool_site *o
  * scaffold (a row of DSTdb), bit 1 it owns the site, bits 2..4 the own row's class, bits 5..6 its con_base */
 int isx_cmpset_pool_fetch_sample(isx_cmpset *set, int32_t sample, uint32_t *counts, uint8_t *meta);
 
+/* ---- strain clustering per genome (`inStrain compare`'s strain_clusters.tsv: compare_controller.py:292-332, 435-450,
+ *      compare_utils.py:169-284 cluster_genome_strains, genomeUtilities.py:739-800 with mm_level off; scipy.cluster.hierarchy
+ *      linkage + fcluster(criterion='distance')) ----
+ * A problem is n points (2 .. ISX_CLUSTER_MAX_POINTS) with a condensed distance matrix (scipy's order: (0,1), (0,2), .. (n-2,n-1)).
+ * The linkage is scipy's NN-chain, restated: from the chain's last cluster the nearest live cluster in index order, strictly smaller
+ * wins, the chain's previous element wins ties; a mutual pair is merged (the lower index dies), rows updated by the method's formula;
+ * the n - 1 merges are sorted by height (stable) and relabelled (merge k = cluster n + k, the smaller id left).  Flat clusters: the
+ * first node from the root whose largest height below it is <= cutoff opens a cluster; numbers in scipy's walk order, from 1.
+ * method: "average", "complete" or "weighted"; "single", "centroid", "median", "ward" (other algorithms in scipy) and anything else are
+ * ISX_ERR_ARG by name.  fp64, one operation at a time, no atomics: the bytes equal scipy's and two calls give identical bytes.
+ * One problem per wave up to 64 points, per 256-thread workgroup beyond; the matrix lives in LDS up to ISX_CLUSTER_LDS_MAX_POINTS points,
+ * in a global workspace (chunks of problems) beyond.  Every device loop is bounded; a problem that leaves its bounds is ISX_ERR_HIP. */
+#define ISX_CLUSTER_MAX_POINTS 1024     /* more points in one problem (samples in a set): ISX_ERR_CAPACITY */
+#define ISX_CLUSTER_LDS_MAX_POINTS 128  /* largest problem whose matrix is kept in LDS (65 024 bytes) */
+#define ISX_CLUSTER_OK 0                /* isx_cluster_status.status: clustered */
+#define ISX_CLUSTER_NO_OVERLAP 1        /* not clustered: a pair of the genome has compared_bases_count 0 (evalute_genome_dist_matrix) */
+#define ISX_CLUSTER_MISSING_PAIR 2      /* not clustered: two of the genome's samples share no row (the reference hands scipy a NaN and raises) */
+#define ISX_CLUSTER_EMPTY 3             /* the genome has no row at all */
+#define ISX_CLUSTER_ERROR 4             /* internal: a device loop reached its bound (the call returns ISX_ERR_HIP) */
+typedef struct {
+    int32_t status, n_points;   /* ISX_CLUSTER_*; the genome's samples */
+} isx_cluster_status;
+typedef struct {
+    int64_t tcb;                /* compared_bases_count summed over the pair's rows of the genome */
+    double w;                   /* sum of ((both - population_snps) / both) * both over the rows with both > 0, in set order; popANI = w / tcb */
+    int32_t n_rows, pad;        /* rows (scaffolds both samples have, not failed); 0: the pair was never compared on the genome */
+} isx_genome_pair;              /* 24 bytes */
+
+/* A batch of problems from host matrices.  n_points[n_problems]; offsets[n_problems] = first value of every problem's condensed matrix
+ * in values[n_values] (n (n - 1) / 2 values each, which must lie inside; all finite -- both checked before anything is launched, ISX_ERR_ARG).
+ * labels: the points of problem 0, then of problem 1, ...; Z (or NULL): [sum of (n - 1)][4] rows as scipy's linkage, problem after problem. */
+int isx_cluster_linkage(isx_ctx *ctx, int32_t n_problems, const int32_t *n_points, const int64_t *offsets, const double *values,
+                        int64_t n_values, const char *method, double cutoff, int32_t *labels, double *Z, float *device_ms);
+
+/* The genomes of a set from the counters the last isx_cmpset_compare left on the device (none since the last add: ISX_ERR_STATE).
+ * scaffold_genome[n_scaffolds]: genome 0 .. n_genomes - 1 of every set scaffold, -1 = in no genome (left out); genome_lengths[n_genomes]
+ * (percent_compared = tcb / length); sample_rank[n_samples]: the place of every sample in the order of the names (a permutation).
+ * Per (genome, pair): the rows are the scaffolds both samples have and no pair failed on, each at the highest axis level that is a key of
+ * either sample; tcb, w as isx_genome_pair.  A genome's points are the samples with a row, by rank.  distance = 1 when
+ * percent_compared < coverage_treshold, else 1 - w / tcb.  status[n_genomes]; labels[n_genomes][n_samples], 0 = not a point of the genome
+ * (or the genome was not clustered). */
+int isx_cmpset_cluster(isx_cmpset *set, int32_t n_genomes, const int32_t *scaffold_genome, const double *genome_lengths,
+                       const int32_t *sample_rank, const char *method, double cutoff, double coverage_treshold, isx_cluster_status *status,
+                       int32_t *labels, float *device_ms);
+/* of the last isx_cmpset_cluster (none since the last add / compare: ISX_ERR_STATE): out[n_genomes][n_pairs], pairs as isx_cmpset_compare */
+int isx_cmpset_cluster_fetch_pairs(isx_cmpset *set, isx_genome_pair *out);
+/* ... and Z[n_points - 1][4] of one clustered genome (points numbered in rank order) */
+int isx_cmpset_cluster_fetch_linkage(isx_cmpset *set, int32_t genome, double *Z);
+
 /* ---- gene profiling (GeneProfile.py:304-707 profile_genes_from_profile: `inStrain profile -g genes.fna`) ----
  * A gene set lives on the device for as long as the caller keeps it: coordinates + the genes' own letters (upper-case
  * A/C/G/T/N as in the .fna, gene orientation), uploaded once.  Genes of one scaffold are consecutive in the set.

@@ -161,6 +161,13 @@ POOL_SITE_DT = np.dtype([("gpos", "<u4"), ("n_detect", "<u4"), ("cnt", "<u8", (4
                          ("pad", "u1", (5,))])          # isx_pool_site
 assert POOL_SITE_DT.itemsize == 64
 POOL_META_HAS, POOL_META_OWN = 1, 2             # isx_cmpset_pool_fetch_sample meta bits; then cls << 2, con_base << 5
+CLUSTER_MAX_POINTS = 1024       # ISX_CLUSTER_MAX_POINTS
+CLUSTER_LDS_MAX_POINTS = 128    # ISX_CLUSTER_LDS_MAX_POINTS: the largest problem whose distance matrix is kept in LDS
+CLUSTER_METHODS = ("average", "complete", "weighted")
+CLUSTER_OK, CLUSTER_NO_OVERLAP, CLUSTER_MISSING_PAIR, CLUSTER_EMPTY = 0, 1, 2, 3       # isx_cluster_status.status
+CLUSTER_STATUS_DT = np.dtype([("status", "<i4"), ("n_points", "<i4")])                  # isx_cluster_status
+GENOME_PAIR_DT = np.dtype([("tcb", "<i8"), ("w", "<f8"), ("n_rows", "<i4"), ("pad", "<i4")])    # isx_genome_pair
+assert GENOME_PAIR_DT.itemsize == 24
 
 
 GENE_DT = np.dtype([("start", "<i8"), ("end", "<i8"), ("seq_off", "<i8"), ("strand", "<i4"), ("pad", "<i4")])
@@ -187,6 +194,7 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
            "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
            "isx_cmpset_pool_enable", "isx_cmpset_pool_sites", "isx_cmpset_pool_fetch_sites", "isx_cmpset_pool_add", "isx_cmpset_pool_summary", "isx_cmpset_pool_fetch_sample",
+           "isx_cluster_linkage", "isx_cmpset_cluster", "isx_cmpset_cluster_fetch_pairs", "isx_cmpset_cluster_fetch_linkage",
            "isx_irep_layout", "isx_irep_create", "isx_irep_destroy", "isx_irep_sizes", "isx_irep_add", "isx_irep_blocks_fetch", "isx_irep_blocks_add", "isx_irep_finish",
            "isx_genes_create", "isx_genes_destroy", "isx_genes_sites", "isx_batch_profile_genes", "isx_genes_profile_snvs",
            "isx_pipe_create", "isx_pipe_destroy", "isx_pipe_submit", "isx_pipe_submit_reads", "isx_pipe_stage_reads", "isx_pipe_submit_wire", "isx_wire_bytes", "isx_wire_free", "isx_wire_keep_reference", "isx_pipe_submit_bam", "isx_encode_segs", "isx_encode_segs_ring", "isx_seg_records_needed", "isx_encode_delta", "isx_delta_records_needed", "isx_count_read_segs", "isx_pack_reads", "isx_pipe_collect", "isx_pipe_release", "isx_pipe_fetch_entries", "isx_pipe_fetch_entries_shrunk", "isx_levels_expand", "isx_encode_obs", "isx_encode_obs_ring",
@@ -279,6 +287,10 @@ def load():
     lib.isx_cmpset_pool_add.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.isx_cmpset_pool_summary.argtypes = [vp, i64, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_pool_fetch_sample.argtypes = [vp, i32, vp, vp]
+    lib.isx_cluster_linkage.argtypes = [vp, i32, vp, vp, vp, i64, C.c_char_p, C.c_double, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_cmpset_cluster.argtypes = [vp, i32, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_cmpset_cluster_fetch_pairs.argtypes = [vp, vp]
+    lib.isx_cmpset_cluster_fetch_linkage.argtypes = [vp, i32, vp]
     lib.isx_irep_layout.argtypes = [i32, vp, vp, i32, i32, vp, vp, vp]
     lib.isx_irep_create.argtypes = [vp, i32, vp, vp, i32, i32, C.POINTER(vp)]
     lib.isx_irep_destroy.argtypes = [vp]

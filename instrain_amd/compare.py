@@ -15,6 +15,10 @@ A whole sample set (every pair of every scaffold, compare_controller.py:611-658)
 device (isx_cmpset_*: one bit per position and level, the covT-key flags, the last SNV row of every position), so batches -- pipe
 slots included -- can go as soon as they have been added; compare() then counts all pairs in one pass.  genome_wide() is
 genomeUtilities._genome_wide_readComparer (genomeUtilities.py:739-800) after _add_stb (:430-448), on the host.
+
+Strain clustering (strain_clusters.tsv; compare_utils.py:205-255 cluster_genome_strains): SampleSet.strain_clusters()
+from the counters compare() left on the device, cluster_genome_strains() from a genome_wide / stored genomeWide_compare frame,
+linkage_flat() from plain matrices -- all three through the same kernel (isx_cluster.hip); there is no host path that clusters.
 """
 import ctypes as C
 import itertools
@@ -150,6 +154,7 @@ class SampleSet:
         self.samples = []
         self.failed = set()                                     # scaffolds on which a pair of the last compare() failed
         self.device_ms, self.levels = 0.0, None
+        self.cluster_genomes, self.cluster_status, self.cluster_labels, self.cluster_device_ms = [], None, None, 0.0   # of the last strain_clusters()
         h = C.c_void_p()
         check(self.lib.isx_cmpset_create(ctx.h, len(self.names), self.lengths.ctypes.data, int(min_cov), C.byref(h)))
         self.h = h
@@ -303,6 +308,54 @@ class SampleSet:
         pm["var_base"] = BASES[summary["var_base"]]
         return dst, pm
 
+    # ---- strain clustering (compare_utils.py:205-255; include/instrain_amd.h isx_cmpset_cluster) ----
+    def strain_clusters(self, stb, bin2length=None, ani_threshold=0.99999, coverage_treshold=0.1, clusterAlg="average", logs=None):
+        """-> Cdb (cluster, sample, genome) of the genomes `stb` (scaffold -> genome) makes of the set's scaffolds, from the counters of
+        the last compare() (needed since the last add_batch).  bin2length: genome -> length, None = the summed lengths of the genome's
+        scaffolds in the set.  A genome with a pair that compared no base (the reference's rule) or with two samples that share no
+        scaffold of it (the reference raises there) is left out with a line in `logs`; the others are numbered 1, 2, ... in sorted order."""
+        import pandas as pd
+        _cluster_method(clusterAlg)
+        genome_of = [stb.get(n) for n in self.names]
+        genomes = sorted({g for g in genome_of if g is not None})
+        self.cluster_genomes, self.cluster_status, self.cluster_labels = genomes, None, None
+        if not genomes:                                         # (stb names no scaffold of the set)
+            return pd.DataFrame({"cluster": [], "sample": [], "genome": []})
+        at = {g: i for i, g in enumerate(genomes)}
+        sg = np.array([-1 if g is None else at[g] for g in genome_of], dtype=np.int32)
+        if bin2length is None:
+            lengths = np.bincount(sg[sg >= 0], weights=self.lengths[sg >= 0], minlength=len(genomes)).astype(np.float64)
+        else:
+            lengths = np.array([bin2length.get(g, np.nan) for g in genomes], dtype=np.float64)
+        S = len(self.samples)
+        order = sorted(range(S), key=lambda i: self.samples[i])
+        rank = np.zeros(max(S, 1), dtype=np.int32)
+        rank[order] = np.arange(S, dtype=np.int32)
+        status = np.zeros(len(genomes), dtype=_lib.CLUSTER_STATUS_DT)
+        labels = np.zeros((len(genomes), max(S, 1)), dtype=np.int32)
+        ms = C.c_float(0)
+        check(self.lib.isx_cmpset_cluster(self.h, len(genomes), sg.ctypes.data, lengths.ctypes.data, rank.ctypes.data, clusterAlg.encode(),
+                                          1.0 - float(ani_threshold), float(coverage_treshold), status.ctypes.data, labels.ctypes.data,
+                                          C.byref(ms)))
+        self.cluster_device_ms, self.cluster_status, self.cluster_labels = ms.value, status, labels
+        by_rank = labels[:, order]                              # columns in the order of the names
+        return _cdb(genomes, status["status"], by_rank, np.array(self.samples, dtype=object)[order], logs)
+
+    def cluster_pairs(self):
+        """the genome roll-up of the last strain_clusters(): GENOME_PAIR_DT [genome in .cluster_genomes order, pair as
+        itertools.combinations of .samples]"""
+        S = len(self.samples)
+        out = np.zeros((len(self.cluster_genomes), S * (S - 1) // 2), dtype=_lib.GENOME_PAIR_DT)
+        check(self.lib.isx_cmpset_cluster_fetch_pairs(self.h, out.ctypes.data))
+        return out
+
+    def cluster_linkage(self, genome):
+        """Z (scipy's linkage matrix) of one clustered genome of the last strain_clusters(); points = its samples sorted by name"""
+        g = self.cluster_genomes.index(genome)
+        Z = np.zeros((max(int(self.cluster_status["n_points"][g]) - 1, 1), 4), dtype=np.float64)
+        check(self.lib.isx_cmpset_cluster_fetch_linkage(self.h, g, Z.ctypes.data))
+        return Z[:int(self.cluster_status["n_points"][g]) - 1]
+
     def close(self):
         if self.h:
             self.lib.isx_cmpset_destroy(self.h)
@@ -359,6 +412,132 @@ def genome_wide(table, stb, bin2length=None, mm_level=False):
     if not mm_level:
         del db["mm"]
     return db
+
+
+# ---- strain clustering (compare_utils.py:169-284) ----
+def _cluster_method(name):
+    if name not in _lib.CLUSTER_METHODS:
+        raise ValueError("clusterAlg %r is not supported: %s are (scipy runs other algorithms than the NN-chain for single, centroid, "
+                         "median and ward)" % (name, ", ".join(_lib.CLUSTER_METHODS)))
+    return name.encode()
+
+
+def cluster_skip_line(genome, status):
+    """the log line of a genome that is not clustered"""
+    if status == _lib.CLUSTER_NO_OVERLAP:                       # (the reference's line, compare_utils.py:263, without its counts)
+        return "Cannot cluster genome %s; some comparisons involve no genomic overlap at all" % (genome,)
+    return "Cannot cluster genome %s; some pair of its samples was never compared (not every pair shares a scaffold of it)" % (genome,)
+
+
+def _cdb(genomes, status, labels, names, logs):
+    """genomes sorted, status[genome], labels[genome, sample by name] (0 = not a member), names sorted -> Cdb"""
+    import pandas as pd
+    status = np.asarray(status)
+    if logs is not None:
+        for g in np.flatnonzero((status == _lib.CLUSTER_NO_OVERLAP) | (status == _lib.CLUSTER_MISSING_PAIR)):
+            logs.append(cluster_skip_line(genomes[g], int(status[g])))
+    number = np.cumsum(status == _lib.CLUSTER_OK)               # the genomes actually clustered count from 1
+    lab = np.where((status == _lib.CLUSTER_OK)[:, None], labels, 0)
+    gi, si = np.nonzero(lab)
+    cluster = np.char.add(np.char.add(number[gi].astype(str), "_"), lab[gi, si].astype(str)).astype(object) if len(gi) else np.zeros(0, object)
+    return pd.DataFrame({"cluster": cluster, "sample": np.asarray(names, dtype=object)[si], "genome": np.asarray(genomes, dtype=object)[gi]})
+
+
+def _linkage_batch(ctx, n_points, offsets, values, method, cutoff, want_Z=True):
+    """isx_cluster_linkage -> (labels of problem 0, 1, ... in one array, Z rows or None, device ms)"""
+    n_points = np.ascontiguousarray(n_points, dtype=np.int32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    n_pts = int(n_points.astype(np.int64).sum())
+    labels = np.zeros(max(n_pts, 1), dtype=np.int32)
+    Z = np.zeros((max(n_pts - len(n_points), 1), 4), dtype=np.float64) if want_Z else None
+    ms = C.c_float(0)
+    check(ctx.lib.isx_cluster_linkage(ctx.h, len(n_points), n_points.ctypes.data, offsets.ctypes.data, values.ctypes.data, len(values),
+                                      method if isinstance(method, bytes) else str(method).encode(), float(cutoff), labels.ctypes.data,
+                                      None if Z is None else Z.ctypes.data, C.byref(ms)))
+    return labels[:n_pts], (None if Z is None else Z[:n_pts - len(n_points)]), ms.value
+
+
+def linkage_flat(ctx, matrices, method, cutoff):
+    """scipy.cluster.hierarchy.linkage(m, method) + fcluster(Z, cutoff, criterion='distance') for a batch of distance matrices (square
+    and symmetric with a zero diagonal, or condensed) on the device -> [(labels int32[n], Z float64[n - 1, 4])], bit-equal to scipy's"""
+    _cluster_method(method)
+    cond, n_points = [], []
+    for k, m in enumerate(matrices):
+        m = np.asarray(m, dtype=np.float64)
+        if m.ndim == 2:
+            if m.shape[0] != m.shape[1] or not (np.array_equal(m, m.T, equal_nan=True) and (np.diagonal(m) == 0).all()):
+                raise ValueError("linkage_flat: matrix %d is not square and symmetric with a zero diagonal" % k)
+            n = m.shape[0]
+            m = m[np.triu_indices(n, 1)]
+        elif m.ndim == 1:
+            n = int(round((1 + np.sqrt(1 + 8 * len(m))) / 2))
+            if n * (n - 1) // 2 != len(m):
+                raise ValueError("linkage_flat: %d values are no condensed distance matrix (matrix %d)" % (len(m), k))
+        else:
+            raise ValueError("linkage_flat: matrix %d has %d dimensions" % (k, m.ndim))
+        cond.append(m)
+        n_points.append(n)
+    if not cond:
+        return []
+    offsets = np.r_[0, np.cumsum([len(c) for c in cond])][:-1]
+    labels, Z, _ = _linkage_batch(ctx, n_points, offsets, np.concatenate(cond), method, cutoff)
+    p0 = np.r_[0, np.cumsum(n_points)]
+    return [(labels[p0[k]:p0[k + 1]].copy(), Z[p0[k] - k:p0[k + 1] - k - 1].copy()) for k in range(len(cond))]
+
+
+def cluster_genome_strains(ctx, Mdb, ani_threshold=0.99999, coverage_treshold=0.1, clusterAlg="average", logs=None, details=None):
+    """compare_utils.cluster_genome_strains (compare_utils.py:205-255) on a genome_wide() / stored genomeWide_compare frame (columns genome,
+    name1, name2, compared_bases_count, popANI, percent_compared) -> Cdb (cluster, sample, genome).  The matrices are made here by
+    numpy / pandas, every genome's linkage and flat clusters on the device (isx_cluster_linkage) in one call.  Genomes that cannot be
+    clustered are left out with a line in `logs` (see SampleSet.strain_clusters).  details: a dict that receives genomes, status,
+    samples, matrices (condensed), Z and device_ms of the call."""
+    import pandas as pd
+    method = _cluster_method(clusterAlg)
+    for c in ("genome", "name1", "name2", "compared_bases_count", "popANI", "percent_compared"):
+        if c not in Mdb.columns:
+            raise ValueError("cluster_genome_strains: the table has no column %r (genome_wide needs bin2length for percent_compared)" % c)
+    db = Mdb[Mdb["name1"] != Mdb["name2"]]
+    gcode, genomes = pd.factorize(db["genome"], sort=True)
+    G = len(genomes)
+    # rule 2: a genome's samples, sorted by name
+    pts = pd.DataFrame({"g": np.r_[gcode, gcode], "s": np.r_[db["name1"].to_numpy(dtype=object), db["name2"].to_numpy(dtype=object)]})
+    pts = pts.drop_duplicates().sort_values(["g", "s"], kind="stable").reset_index(drop=True)
+    n_of = np.bincount(pts["g"].to_numpy(), minlength=G).astype(np.int64)
+    pt_off = np.r_[0, np.cumsum(n_of)]
+    where = pd.MultiIndex.from_arrays([pts["g"], pts["s"]])
+    a = where.get_indexer(pd.MultiIndex.from_arrays([gcode, db["name1"].to_numpy(dtype=object)])) - pt_off[gcode]
+    b = where.get_indexer(pd.MultiIndex.from_arrays([gcode, db["name2"].to_numpy(dtype=object)])) - pt_off[gcode]
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    # rules 3, 4
+    n_val = n_of * (n_of - 1) // 2
+    val_off = np.r_[0, np.cumsum(n_val)]
+    values = np.full(int(val_off[-1]), np.nan)
+    pc = db["percent_compared"].to_numpy(dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        dist = np.where(pc < coverage_treshold, 1.0, 1.0 - db["popANI"].to_numpy(dtype=np.float64))
+    values[val_off[gcode] + n_of[gcode] * lo - lo * (lo + 1) // 2 + (hi - lo - 1)] = dist
+    status = np.full(G, _lib.CLUSTER_OK, dtype=np.int32)
+    holes = np.add.reduceat(np.r_[np.isnan(values), False].astype(np.int64), val_off[:-1])[:G] if G else np.zeros(0, np.int64)
+    status[(holes > 0) & (n_val > 0)] = _lib.CLUSTER_MISSING_PAIR
+    status[np.bincount(gcode, weights=(db["compared_bases_count"].to_numpy() == 0), minlength=G) > 0] = _lib.CLUSTER_NO_OVERLAP
+    ok = np.flatnonzero(status == _lib.CLUSTER_OK)
+    S_all = pts["s"].to_numpy(dtype=object)
+    names = sorted(set(S_all.tolist()))
+    col = pd.Index(names).get_indexer(S_all)
+    labels = np.zeros((G, max(len(names), 1)), dtype=np.int32)
+    Z, ms = None, 0.0
+    if len(ok):
+        keep = np.repeat(status == _lib.CLUSTER_OK, n_of)
+        flat, Z, ms = _linkage_batch(ctx, n_of[ok], val_off[ok], values, method, 1.0 - float(ani_threshold))
+        labels[pts["g"].to_numpy()[keep], col[keep]] = flat
+    if details is not None:
+        z0 = np.r_[0, np.cumsum(n_of[ok] - 1)]
+        details.update(genomes=list(genomes), status=status, device_ms=ms,
+                       samples={genomes[g]: S_all[pt_off[g]:pt_off[g + 1]].tolist() for g in range(G)},
+                       matrices={genomes[g]: values[val_off[g]:val_off[g + 1]].copy() for g in range(G)},
+                       Z={genomes[g]: Z[z0[k]:z0[k + 1]].copy() for k, g in enumerate(ok)})
+    return _cdb(list(genomes), status, labels, names, logs)
 
 
 # ---- the user tables of SNV pooling (SNVprofile.py:367-410) ----

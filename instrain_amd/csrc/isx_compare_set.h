@@ -122,6 +122,12 @@ struct isx_cmpset {
     isxset::SetBuf<int64_t> d_pwoff;                // [n_scaf + 1]
     isxset::SetBuf<uint32_t> d_srank, d_own;        // [n_scaf + 1]; [samples][n_scaf] own rows
     isxset::SetBuf<isx_pool_site> d_psum;
+    // strain clustering (isx_cluster.hip).  clustered: isx_cmpset_cluster has run since the last add / compare
+    bool clustered = false;
+    int64_t cl_P = 0;
+    std::vector<isx_cluster_status> cl_status;      // [genomes of the call]
+    isxset::SetBuf<isx_genome_pair> d_gpairs;       // [genomes][pairs] the roll-up
+    isxset::SetBuf<double> d_clZ;                   // [genomes][samples - 1][4]
 };
 
 // isx_compare_set.hip, for isx_compare_pool.hip
@@ -132,4 +138,5 @@ int cmpset_check_batch(const char *who, const isx_cmpset *st, int32_t sample, co
 int cmpset_grow_temp(isx_cmpset *st, size_t bytes);
 void cmpset_pool_drop(isx_cmpset *st);          // isx_compare_pool.hip: frees every pooling array of the set (not the samples' pool rows)
 int cmpset_sort_pool_rows(isx_cmpset *st, Sample &sm);
+void cmpset_cluster_drop(isx_cmpset *st);       // isx_cluster.hip: frees what the last isx_cmpset_cluster left
 }

@@ -426,6 +426,7 @@ void isx_cmpset_destroy(isx_cmpset *st)
         if (s.prows) isx_dev_free(s.prows);
     }
     cmpset_pool_drop(st);
+    cmpset_cluster_drop(st);
     st->cov.drop(); st->present.drop(); st->idx.drop(); st->idx_in.drop(); st->flags.drop(); st->pos.drop(); st->scratch_f.drop();
     st->bbounds.drop(); st->set_pos0.drop(); st->acc.drop(); st->temp.drop(); st->jobs.drop(); st->keys.drop(); st->keys_in.drop();
     st->d_planes.drop(); st->d_rows.drop(); st->d_n_rows.drop(); st->d_failed.drop(); st->d_cursor.drop(); st->d_lmap.drop();
@@ -499,6 +500,7 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
         sm.present.assign((size_t)st->n_scaf * M, 0);
     }
     st->compared = false;
+    st->clustered = false;
     st->pooled = false;                             // the sites, ranks and pulled counts of isx_cmpset_pool_sites are of the set as it was
     // scratch, all sized before anything is launched
     HIP_TRY(st->cov.fit(n_pos)); HIP_TRY(st->scratch_f.fit((size_t)n_pos * 2));
@@ -619,6 +621,7 @@ int isx_cmpset_compare(isx_cmpset *st, double min_freq, int64_t cap_rows, isx_co
     if (n_pairs * n_scaf * A > cap_rows) { isx_set_error("isx_cmpset_compare: out holds fewer than pairs x scaffolds x levels rows"); return ISX_ERR_ARG; }
     if (device_ms) *device_ms = 0.f;
     st->compared = false;
+    st->clustered = false;
     if (n_pairs == 0 || A == 0) return ISX_OK;
     HIP_TRY(hipSetDevice(st->ctx->device));
     hipStream_t s = st->ctx->stream;
