@@ -491,6 +491,38 @@ void isx_cmpset_destroy(isx_cmpset *set);
 int isx_cmpset_add(isx_cmpset *set, int32_t sample, isx_batch *batch, int32_t n_batch_scaffolds, const int64_t *batch_scaffold_bounds,
                    const int32_t *set_scaffold_ids, const int32_t *level_mm_values);
 
+/* The second way into a set: a STORED profile of the sample (compare_controller.py:520-577: covT of raw_data/covT.hd5 and the
+ * cumulative_snv_table) instead of a resident batch.  It leaves exactly what isx_cmpset_add leaves -- the per-level bit planes, the
+ * per-(scaffold, level) key flags, the last SNV row of every position -- so nothing downstream can tell how a sample arrived, and a
+ * sample may be fed scaffold by scaffold through both entry points.
+ *   set_scaffold_ids[n_scaffolds]   the set's scaffold that scaffold i of THIS call is, -1 = not in the set: skipped
+ *   level_mm_values[n_levels]       the SAMPLE's levels, real mm strictly ascending within 0..65535, at most ISX_CMPSET_MAX_LEVELS
+ *                                   (more: ISX_ERR_CAPACITY); every call for a sample (either entry point) brings the same values
+ *   present[n_scaffolds][n_levels]  the level's mm is a key of covT[scaffold]
+ *   entry_offsets[n_scaffolds * n_levels + 1]   CSR over (scaffold, level) into positions / values: one covT series after another,
+ *                                   index and value.  Positions of a series ascend strictly and stay below the set's length of the
+ *                                   scaffold (else ISX_ERR_ARG); a series under present == 0 must be empty; an empty series under a
+ *                                   present level is legal (the key exists).  Values add up over the levels clamped at min_cov, so
+ *                                   any uint32 is safe.
+ *   snv[n_snv]                      rows of the stored cumulative_snv_table, in any order; a scaffold index outside the call, a position
+ *                                   outside the scaffold, an mm outside 0..65535 or a base code outside its range is ISX_ERR_ARG; rows of
+ *                                   a scaffold with set_scaffold_ids -1 are skipped.  Kept: the highest-mm row of every position,
+ *                                   whether or not that mm is a level (compare_utils.py:124-138, readComparer.py:236-247).
+ * The same (sample, scaffold) twice is ISX_ERR_STATE, as is a set with pooling enabled (its own rows need the class / cryptic columns
+ * and the pull needs reads).  A call with no scaffold of the set returns ISX_OK and does nothing.  All arguments are checked on the
+ * host before anything is launched: a refused call leaves the set as it was.  *device_ms (may be NULL): the event-timed device pass. */
+typedef struct {              /* one row of a stored cumulative_snv_table; 32 bytes */
+    int32_t  scaffold;        /* index into THIS call's scaffold list */
+    uint32_t position;        /* on the scaffold */
+    int32_t  mm;              /* real mm, 0..65535 */
+    uint8_t  con_base, ref_base, var_base, allele_count;   /* 0..3 = A C T G; ref_base 4 = N */
+    uint32_t cnt[4];          /* A C T G */
+} isx_profile_snv;
+int isx_cmpset_add_profile(isx_cmpset *set, int32_t sample, int32_t n_scaffolds, const int32_t *set_scaffold_ids, int32_t n_levels,
+                           const int32_t *level_mm_values, const uint8_t *present, const int64_t *entry_offsets,
+                           const uint32_t *positions, const uint32_t *values, int64_t n_snv, const isx_profile_snv *snv,
+                           float *device_ms);
+
 /* sizes of the next isx_cmpset_compare (readComparer.py:162 over all samples): samples (highest index added + 1), axis levels, their real mm values (axis_mm[ISX_CMPSET_MAX_LEVELS] or NULL) */
 int isx_cmpset_axis(isx_cmpset *set, int32_t *n_samples, int32_t *n_levels, int32_t *axis_mm);
 

@@ -156,6 +156,9 @@ assert IREP_GENOME_DT.itemsize == 48 and IREP_ROW_DT.itemsize == 96
 IREP_FAIL_KEPT, IREP_FAIL_COV, IREP_FAIL_R2, IREP_FAIL_FRAG, IREP_EMPTY, IREP_NO_FIT = 1, 2, 4, 8, 16, 32       # isx_irep_row.flags
 CMPSET_TILE_DT = np.dtype([("word0", "<i8"), ("n_words", "<i4"), ("scaffold", "<i4")])      # isx_cmpset_tile
 CMPSET_MAX_LEVELS = 128         # ISX_CMPSET_MAX_LEVELS
+PROFILE_SNV_DT = np.dtype([("scaffold", "<i4"), ("position", "<u4"), ("mm", "<i4"), ("con_base", "u1"), ("ref_base", "u1"), ("var_base", "u1"),
+                           ("allele_count", "u1"), ("cnt", "<u4", (4,))])             # isx_profile_snv
+assert PROFILE_SNV_DT.itemsize == 32
 POOL_SITE_DT = np.dtype([("gpos", "<u4"), ("n_detect", "<u4"), ("cnt", "<u8", (4,)), ("n_detect_5x", "<u4"), ("cls_count", "<u2", (5,)),
                          ("ref_base", "u1"), ("con_base", "u1"), ("var_base", "u1"), ("n_con_bases", "u1"), ("con_bases", "u1"),
                          ("pad", "u1", (5,))])          # isx_pool_site
@@ -192,7 +195,7 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_batch_create", "isx_batch_create_reads", "isx_batch_destroy", "isx_batch_run", "isx_batch_launch", "isx_batch_wait", "isx_batch_sizes", "isx_batch_timings", "isx_batch_link_chain",
            "isx_batch_fetch_entries", "isx_batch_fetch_dense", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs",
            "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
-           "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
+           "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_add_profile", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
            "isx_cmpset_pool_enable", "isx_cmpset_pool_sites", "isx_cmpset_pool_fetch_sites", "isx_cmpset_pool_add", "isx_cmpset_pool_summary", "isx_cmpset_pool_fetch_sample",
            "isx_cluster_linkage", "isx_cmpset_cluster", "isx_cmpset_cluster_fetch_pairs", "isx_cmpset_cluster_fetch_linkage",
            "isx_irep_layout", "isx_irep_create", "isx_irep_destroy", "isx_irep_sizes", "isx_irep_add", "isx_irep_blocks_fetch", "isx_irep_blocks_add", "isx_irep_finish",
@@ -277,6 +280,7 @@ def load():
     lib.isx_cmpset_destroy.argtypes = [vp]
     lib.isx_cmpset_destroy.restype = None
     lib.isx_cmpset_add.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    lib.isx_cmpset_add_profile.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_axis.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp]
     lib.isx_cmpset_compare.argtypes = [vp, C.c_double, i64, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_pair_snps.argtypes = [vp, i32, i32, C.POINTER(i64)]

@@ -135,9 +135,162 @@ def level_map(sample_mm_values, cap_axis=_lib.CMPSET_MAX_LEVELS):
     return axis[:n_axis.value].copy(), lmap[:, :n_axis.value].copy()
 
 
+# ---- stored profiles (compare_controller.py:520-577: covT of raw_data/covT.hd5 and the cumulative_snv_table) ----
+SNV_OLD_NAMES = {"conBase": "con_base", "refBase": "ref_base", "varBase": "var_base", "baseCoverage": "position_coverage"}  # (:544-546)
+_BASE_CODE = {"A": 0, "C": 1, "T": 2, "G": 3, "N": 4}
+
+
+def _whole(a, what, top):
+    """an array of whole numbers within 0..top -> int64; ValueError otherwise (NaN, fractions, negatives, text)"""
+    a = np.asarray(a)
+    if a.dtype.kind == "f":
+        if not np.isfinite(a).all() or (a != np.floor(a)).any():
+            raise ValueError("pack_profile: %s holds NaN or a value that is no whole number" % what)
+    elif a.dtype.kind not in "iu":
+        raise ValueError("pack_profile: %s is not numeric (%s)" % (what, a.dtype))
+    if a.size and (a.min() < 0 or a.max() > top):
+        raise ValueError("pack_profile: %s outside 0..%d" % (what, top))
+    return a.astype(np.int64)
+
+
+def _series(ser, what, length):
+    """one covT series (a pd.Series of values indexed by position, or a (positions, values) tuple) -> ascending uint32 pairs"""
+    pos, val = ser if isinstance(ser, tuple) else (ser.index.to_numpy(), ser.to_numpy())
+    pos, val = _whole(pos, what + " positions", length - 1), _whole(val, what + " values", 0xFFFFFFFF)
+    if pos.shape != val.shape or pos.ndim != 1:
+        raise ValueError("pack_profile: %s has not one value per position" % what)
+    if len(pos) > 1 and (pos[1:] <= pos[:-1]).any():
+        order = np.argsort(pos, kind="stable")
+        pos, val = pos[order], val[order]
+        if (pos[1:] == pos[:-1]).any():
+            raise ValueError("pack_profile: %s names a position twice" % what)
+    return pos.astype(np.uint32), val.astype(np.uint32)
+
+
+def pack_profile(index, lengths, covT, snv_table, mm_values=None):
+    """A stored profile as the arrays of isx_cmpset_add_profile; numpy only, no device.
+    index: scaffold name -> scaffold of the set; lengths: the set's lengths.  covT: {scaffold: {mm: pd.Series(values, index=positions)}}
+    (emitters.load_special; (positions, values) tuples are taken too).  snv_table: the cumulative_snv_table (columns scaffold, position,
+    mm, con_base, ref_base, var_base, allele_count, A, C, T, G; the old names conBase / refBase / varBase / baseCoverage are renamed as
+    the reference does), an empty frame or None.  mm_values: the sample's levels, None = the sorted union of the covT keys over the
+    scaffolds the set names.
+    -> {"scaffolds": names, in set order; "ids" int32; "levels" int32; "present" uint8 [scaffold, level]; "offsets" int64 (CSR over
+    (scaffold, level)); "positions", "values" uint32; "snv" PROFILE_SNV_DT}.  Scaffolds the set does not name or whose covT has no key
+    are left out, SNV rows on them and on scaffolds without a covT entry are dropped (the reference never pairs such a sample there).
+    A series whose index does not ascend is sorted; a position twice or beyond the set's length, a negative / fractional / NaN value, an
+    unknown base letter or a position_coverage other than A + C + T + G raise ValueError."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    kept = sorted((index[n], n) for n, d in (covT or {}).items() if n in index and len(d))
+    names = [n for _, n in kept]
+    keys = {n: {int(mm): ser for mm, ser in covT[n].items()} for n in names}
+    union = sorted({mm for d in keys.values() for mm in d})
+    if mm_values is None:
+        levels = np.array(union, dtype=np.int32)
+    else:
+        levels = np.array(mm_values, dtype=np.int32).reshape(-1)
+        if len(levels) > 1 and (levels[1:] <= levels[:-1]).any():
+            raise ValueError("pack_profile: mm_values must ascend strictly")
+        missing = sorted(set(union) - set(levels.tolist()))
+        if missing:
+            raise ValueError("pack_profile: covT has the keys %s, which mm_values does not name" % missing)
+    L = len(levels)
+    present = np.zeros((len(names), L), dtype=np.uint8)
+    offsets = np.zeros(len(names) * L + 1, dtype=np.int64)
+    pos_parts, val_parts = [np.zeros(0, np.uint32)], [np.zeros(0, np.uint32)]
+    for i, n in enumerate(names):
+        for k, mm in enumerate(levels.tolist()):
+            n_here = 0
+            if mm in keys[n]:
+                present[i, k] = 1
+                p, v = _series(keys[n][mm], "covT[%r][%d]" % (n, mm), int(lengths[index[n]]))
+                pos_parts.append(p)
+                val_parts.append(v)
+                n_here = len(p)
+            offsets[i * L + k + 1] = offsets[i * L + k] + n_here
+    out = {"scaffolds": names, "ids": np.array([i for i, _ in kept], dtype=np.int32), "levels": levels, "present": present,
+           "offsets": offsets, "positions": np.concatenate(pos_parts), "values": np.concatenate(val_parts),
+           "snv": np.zeros(0, dtype=_lib.PROFILE_SNV_DT)}
+    if snv_table is None or len(snv_table) == 0:
+        return out
+    db = snv_table.rename(columns=SNV_OLD_NAMES)
+    need = ["scaffold", "position", "mm", "con_base", "ref_base", "var_base", "allele_count", "A", "C", "T", "G"]
+    lacking = [c for c in need if c not in db.columns]
+    if lacking:
+        raise ValueError("pack_profile: the SNV table has no column %s" % ", ".join(lacking))
+    local = {n: i for i, n in enumerate(names)}
+    sc = np.array([local.get(n, -1) for n in db["scaffold"].astype(object)], dtype=np.int64)
+    db = db[sc >= 0]
+    sc = sc[sc >= 0]
+    rows = np.zeros(len(db), dtype=_lib.PROFILE_SNV_DT)
+    rows["scaffold"] = sc
+    position = _whole(db["position"].to_numpy(), "SNV positions", 0xFFFFFFFF)
+    if (position >= lengths[out["ids"][sc]]).any():
+        raise ValueError("pack_profile: an SNV row lies beyond its scaffold")
+    rows["position"] = position
+    rows["mm"] = _whole(db["mm"].to_numpy(), "SNV mm", 65535)
+    rows["allele_count"] = _whole(db["allele_count"].to_numpy(), "allele_count", 255)
+    for col, top in (("con_base", 3), ("ref_base", 4), ("var_base", 3)):
+        code = np.array([_BASE_CODE.get(b, 9) for b in db[col].astype(object)], dtype=np.int64)
+        if (code > top).any():
+            raise ValueError("pack_profile: %s holds %r" % (col, sorted({str(b) for b, c in zip(db[col].astype(object), code) if c > top})))
+        rows[col] = code
+    for j, b in enumerate("ACTG"):
+        rows["cnt"][:, j] = _whole(db[b].to_numpy(), "the SNV table's column " + b, 0xFFFFFFFF)
+    if "position_coverage" in db.columns:
+        pc = db["position_coverage"].to_numpy()
+        if pc.dtype.kind not in "iuf" or (pc != rows["cnt"].astype(np.int64).sum(axis=1)).any():
+            raise ValueError("pack_profile: position_coverage is not A + C + T + G in every row")
+    out["snv"] = rows
+    return out
+
+
+def _scaffold_profiles(profiles):
+    """scaffold profiles as they come, or profile_bam's {"scaffold.split": SplitObject} merged per scaffold (from_splits)"""
+    from .profile import profile_utilities as pu
+    items = list(profiles.values()) if isinstance(profiles, dict) else list(profiles)
+    if all(hasattr(P, "cumulative_scaffold_table") for P in items):
+        return items
+    by = {}
+    for S in items:
+        by.setdefault(S.scaffold, []).append(S)
+    return [pu.scaffold_profile.from_splits(sorted(parts, key=lambda S: S.split_number)) for parts in by.values()]
+
+
+def store_sample(folder, profiles):
+    """covT.hd5 and cumulative_snv_table.csv.gz of a sample under `folder` (the raw_data folder of the reference's profile, under its
+    names, through profile.emitters).  profiles: the sample's scaffold profiles (scaffold_profile.from_splits), or what profile_bam
+    returns.  -> the two paths"""
+    import os
+    import pandas as pd
+    from .profile import emitters
+    profs = _scaffold_profiles(profiles)
+    covT = {P.scaffold: P.covT for P in profs if P.covT}
+    tables = [P.cumulative_snv_table for P in profs if getattr(P, "cumulative_snv_table", None) is not None and len(P.cumulative_snv_table)]
+    sdb = pd.concat(tables).reset_index(drop=True) if tables else pd.DataFrame()
+    os.makedirs(folder, exist_ok=True)
+    return (emitters.store_special(covT, os.path.join(folder, "covT")),
+            emitters.store_pandas(sdb, os.path.join(folder, "cumulative_snv_table")))
+
+
+def load_sample(folder, scaffolds=None):
+    """-> (covT, snv_table) of a stored sample: `folder` holds covT.hd5 and cumulative_snv_table.csv.gz -- written by store_sample, or the
+    raw_data folder of a profile the reference wrote.  scaffolds: load only these."""
+    import os
+    import pandas as pd
+    from .profile import emitters
+    covT = emitters.load_special(os.path.join(folder, "covT.hd5"), scaffolds=None if scaffolds is None else set(scaffolds))
+    try:
+        sdb = emitters.load_pandas(os.path.join(folder, "cumulative_snv_table.csv.gz"))
+    except pd.errors.EmptyDataError:
+        sdb = pd.DataFrame()
+    if scaffolds is not None and "scaffold" in sdb.columns:
+        sdb = sdb[sdb["scaffold"].isin(set(scaffolds))].reset_index(drop=True)
+    return covT, sdb
+
+
 class SampleSet:
     """The samples of one `inStrain compare` run on the device.  scaffold_names / scaffold_lengths: the scaffolds to compare, in the
-    order of the output.  Samples are numbered in the order of their first add_batch."""
+    order of the output.  Samples are numbered in the order of their first add_batch / add_profile."""
 
     def __init__(self, ctx, scaffold_names, scaffold_lengths, min_cov=5, pooling=False):
         """pooling: also keep every sample's own SNV rows for pool_sites() / pool_add() / pooled_tables() (`compare --bams`)"""
@@ -152,6 +305,8 @@ class SampleSet:
         self.index = {n: i for i, n in enumerate(self.names)}
         self.offsets = set_layout(self.lengths) * 64            # first set position of every scaffold
         self.samples = []
+        self._have = {}                                         # sample -> scaffolds of the set it has brought
+        self.profile_device_ms = 0.0                            # of the last add_profile()
         self.failed = set()                                     # scaffolds on which a pair of the last compare() failed
         self.device_ms, self.levels = 0.0, None
         self.cluster_genomes, self.cluster_status, self.cluster_labels, self.cluster_device_ms = [], None, None, 0.0   # of the last strain_clusters()
@@ -179,6 +334,52 @@ class SampleSet:
         if not known:                                           # (a refused batch leaves the set as it was)
             self.samples.append(sample_name)
         self.n_pool_sites = None                                # (the library has dropped its pooling state)
+        self._have.setdefault(sample_name, set()).update(ids[ids >= 0].tolist())
+
+    def add_profile(self, sample_name, covT, snv_table=None, mm_values=None, max_entries=1 << 26):
+        """a sample from its STORED profile (load_sample, or the reference's covT and cumulative_snv_table) instead of a resident batch:
+        the same sketch, so compare() and everything behind it cannot tell how a sample arrived, and one sample may come scaffold by
+        scaffold through both.  covT, snv_table, mm_values: see pack_profile.  The packed profile goes to the device in chunks of whole
+        scaffolds of at most max_entries coverage entries (a larger scaffold goes alone), which bounds the host staging and the device
+        scratch.  Refused as a whole (the set stays as it was): a set with pooling, other levels than the sample's earlier calls, a
+        scaffold the sample already has.  self.profile_device_ms: the event-timed device passes of the call."""
+        self.add_packed(sample_name, pack_profile(self.index, self.lengths, covT, snv_table, mm_values), max_entries)
+
+    def add_packed(self, sample_name, p, max_entries=1 << 26):
+        """add_profile's second half: p = pack_profile(self.index, self.lengths, ...) of the sample, made earlier"""
+        if self.pooling:                                        # (the library's own refusal, also for a profile with no scaffold of the set)
+            raise _lib.IsxError(-6, "add_profile: a set with pooling takes resident batches only (pooling needs the class / cryptic "
+                                    "columns of the sample's own rows, and reads to pull from)")
+        known = sample_name in self.samples
+        sample = self.samples.index(sample_name) if known else len(self.samples)
+        self.profile_device_ms = 0.0
+        again = sorted(set(p["ids"].tolist()) & self._have.get(sample_name, set()))
+        if again:                                               # (the library would refuse only the chunk that holds it)
+            raise _lib.IsxError(-6, "add_profile: scaffold %s of sample %r was added before" % (self.names[again[0]], sample_name))
+        L, off = len(p["levels"]), p["offsets"]
+        per_scaffold = off[L::L] - off[:-1:L] if L else np.zeros(0, np.int64)
+        i0, n = 0, len(p["ids"])
+        while i0 < n:
+            i1, held = i0 + 1, int(per_scaffold[i0])
+            while i1 < n and held + int(per_scaffold[i1]) <= max_entries:
+                held += int(per_scaffold[i1])
+                i1 += 1
+            e0, e1 = int(off[i0 * L]), int(off[i1 * L])
+            sub_off = np.ascontiguousarray(off[i0 * L:i1 * L + 1] - e0)
+            positions, values = np.ascontiguousarray(p["positions"][e0:e1]), np.ascontiguousarray(p["values"][e0:e1])
+            ids, present = np.ascontiguousarray(p["ids"][i0:i1]), np.ascontiguousarray(p["present"][i0:i1])
+            snv = p["snv"][(p["snv"]["scaffold"] >= i0) & (p["snv"]["scaffold"] < i1)].copy()
+            snv["scaffold"] -= i0
+            ms = C.c_float(0)
+            check(self.lib.isx_cmpset_add_profile(self.h, sample, i1 - i0, ids.ctypes.data, L, p["levels"].ctypes.data, present.ctypes.data,
+                                                  sub_off.ctypes.data, positions.ctypes.data, values.ctypes.data, len(snv),
+                                                  snv.ctypes.data, C.byref(ms)))
+            self.profile_device_ms += ms.value
+            i0 = i1
+        if not known:
+            self.samples.append(sample_name)
+        self.n_pool_sites = None
+        self._have.setdefault(sample_name, set()).update(p["ids"].tolist())
 
     def compare(self, min_freq=0.05, logs=None):
         """-> the comparisonsTable rows (the columns of compare_scaffolds) of every pair of samples over every scaffold both have,

@@ -27,6 +27,12 @@ struct PackJob {                        // one batch scaffold that the set names
     int64_t dst_w0, src0, len;          // first word in the set, first position in the batch, positions
 };
 
+struct ProfTile {                       // one workgroup of k_profile_planes: at most 64 words = 4096 positions of ONE scaffold of the call
+    int64_t word0;                      // first word in the set
+    int32_t n_words, scaf;              // words of the tile; the scaffold's index in the call
+    uint32_t pos0, len;                 // first position of the tile on the scaffold; the scaffold's length
+};
+
 struct Sample {
     std::vector<int32_t> mm;            // real mm of every own level (fixed by the first batch)
     uint64_t *planes = nullptr;         // [levels][n_words]
@@ -92,6 +98,11 @@ struct isx_cmpset {
     isxset::SetBuf<uint8_t> acc, temp;
     isxset::SetBuf<isxset::PackJob> jobs;
     isxset::SetBuf<uint64_t> keys, keys_in;
+    // scratch of isx_cmpset_add_profile: the call's covT series (CSR offsets, index, value), its tiles and its SNV rows
+    isxset::SetBuf<int64_t> pf_off;
+    isxset::SetBuf<uint32_t> pf_pos, pf_val;
+    isxset::SetBuf<isxset::ProfTile> pf_tiles;
+    isxset::SetBuf<isx_profile_snv> pf_snv;
     // what the last isx_cmpset_compare left for isx_cmpset_pair_snps
     bool compared = false;
     double min_freq = 0.05;

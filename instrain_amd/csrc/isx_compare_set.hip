@@ -11,7 +11,9 @@
 //   present[scaffold][level]   the level is a key of the sample's covT on the scaffold (Acc.present of run_compare)
 //   rows[]                the highest-mm SNV row of every position, in set-position order
 //   prows[]               (after isx_cmpset_pool_enable) the highest-mm row that is not cryptic: SNV pooling, isx_compare_pool.hip
-// so a batch can go as soon as it has been added.  The set's position space starts every scaffold on a 64-position word
+// so a batch can go as soon as it has been added.  A sample's STORED profile (covT, cumulative_snv_table: compare_controller.py:520-577)
+// leaves the same three through isx_cmpset_add_profile: k_profile_planes turns the sparse covT series into the planes without a dense
+// coverage array, the SNV tail (reserve_last_rows / launch_last_rows) is shared with isx_cmpset_add.  The set's position space starts every scaffold on a 64-position word
 // (cmpset_layout.cpp): no word belongs to two scaffolds, `both` of a pair is popcount(a & b) word by word.
 // Everything counted here is an integer; sums go through 64-bit integer atomics, so a call's bytes do not depend on timing.
 #include <algorithm>
@@ -69,6 +71,66 @@ __global__ void k_set_keys(const isx_snv *snv, uint32_t n, const int64_t *bbound
     idx[i] = i;
 }
 
+// the same keys for the rows of a stored cumulative_snv_table: the scaffold is named, not found (the host has checked every field)
+__global__ void k_profile_keys(const isx_profile_snv *snv, uint32_t n, const int64_t *set_pos0, int n_cscaf, uint64_t *keys, uint32_t *idx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t sc = snv[i].scaffold;
+    const int64_t p0 = sc >= 0 && sc < n_cscaf ? set_pos0[sc] : -1;
+    keys[i] = p0 >= 0 ? ((uint64_t)(p0 + snv[i].position) << 16) | (uint32_t)(snv[i].mm & 0xFFFF) : ~0ull;
+    idx[i] = i;
+}
+
+// Stored covT -> the sample's planes, with no dense coverage array in global memory.  One workgroup per tile (ProfTile: at most 64
+// words = 4096 positions of one scaffold of the call) keeps the tile's coverage in 16 KiB of LDS counters, zeroed once.  Per level,
+// ascending: its slice of the (scaffold, level) series -- two binary searches on the ascending positions -- is added into the counters
+// (positions are unique within a level: one lane owns a counter, no atomics; the add is clamped at min_cov, which keeps `>= min_cov`
+// exact and cannot wrap), then every wave turns 64 counters at a time into a word by ballot and one lane stores it.  A level that is
+// no key of the scaffold has an empty series: its plane is the carried one.  Bits beyond the scaffold's length stay zero.
+constexpr int PROF_TILE_WORDS = 64;
+constexpr int PROF_TILE_POS = PROF_TILE_WORDS * 64;
+
+__device__ __forceinline__ int64_t first_at_least(const uint32_t *pos, int64_t lo, int64_t hi, uint64_t want)
+{
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((uint64_t)pos[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) k_profile_planes(const ProfTile *tiles, const int64_t *entry_off, int n_levels,
+                                                        const uint32_t *positions, const uint32_t *values, uint32_t min_cov,
+                                                        uint64_t *planes, int64_t n_words)
+{
+    __shared__ uint32_t cov[PROF_TILE_POS];
+    const ProfTile t = tiles[blockIdx.x];
+    const int tw = min(t.n_words, PROF_TILE_WORDS);
+    if (tw <= 0 || t.scaf < 0 || t.word0 < 0 || t.word0 + tw > n_words) return;                         // (block-uniform)
+    const uint32_t n_tile = (uint32_t)tw * 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    for (uint32_t p = threadIdx.x; p < n_tile; p += blockDim.x) cov[p] = 0;
+    for (int lv = 0; lv < n_levels; lv++) {
+        __syncthreads();                    // the counters are zeroed / the words of the level before have been read
+        const int64_t b = entry_off[(int64_t)t.scaf * n_levels + lv], e = entry_off[(int64_t)t.scaf * n_levels + lv + 1];
+        const int64_t k0 = first_at_least(positions, b, e, t.pos0), k1 = first_at_least(positions, k0, e, (uint64_t)t.pos0 + n_tile);
+        for (int64_t k = k0 + threadIdx.x; k < k1; k += blockDim.x) {
+            const uint32_t p = positions[k] - t.pos0, v = values[k];
+            if (p >= n_tile) continue;                                                                  // (the host's checks rule it out)
+            const uint32_t c = cov[p];                                                                  // c <= min_cov
+            cov[p] = c + min(v, min_cov - min(c, min_cov));
+        }
+        __syncthreads();
+        uint64_t *plane = planes + (int64_t)lv * n_words + t.word0;
+        for (int w = wave; w < tw; w += n_waves) {                                                      // wave-uniform
+            const uint32_t p = (uint32_t)w * 64 + lane;
+            const unsigned long long mask = __ballot(cov[p] >= min_cov && (uint64_t)t.pos0 + p < t.len);
+            if (lane == 0) plane[w] = mask;
+        }
+    }
+}
+
 __global__ void k_last_flags(const uint64_t *keys, uint32_t n, uint32_t *flags)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,15 +138,17 @@ __global__ void k_last_flags(const uint64_t *keys, uint32_t n, uint32_t *flags)
     flags[i] = keys[i] != ~0ull && (i + 1 == n || (keys[i + 1] >> 16) != (keys[i] >> 16)) ? 1u : 0u;
 }
 
-// the flagged rows, in key order, behind the sample's earlier rows; total[0] = how many
+// the flagged rows, in key order, behind the sample's earlier rows; total[0] = how many.  Src: isx_snv (a resident batch) or
+// isx_profile_snv (a stored cumulative_snv_table) -- both name the payload fields alike
+template <class Src>
 __global__ void k_gather_last(const uint64_t *keys, const uint32_t *idx, const uint32_t *flags, const uint32_t *pos, uint32_t n,
-                              const isx_snv *snv, CsRow *out, uint32_t cap, uint32_t *total)
+                              const Src *snv, CsRow *out, uint32_t cap, uint32_t *total)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (i + 1 == n) total[0] = pos[i] + flags[i];
     if (!flags[i] || pos[i] >= cap) return;
-    const isx_snv x = snv[idx[i]];
+    const Src x = snv[idx[i]];
     CsRow r;
     r.gpos = (uint32_t)(keys[i] >> 16);
     r.con_base = x.con_base; r.ref_base = x.ref_base; r.var_base = x.var_base; r.allele_count = x.allele_count;
@@ -326,6 +390,47 @@ int level_axis(const isx_cmpset *st, std::vector<int32_t> &axis, int32_t *n_axis
     return isx_cmpset_level_map(S, n_levels.data(), all.data(), ISX_CMPSET_MAX_LEVELS, axis.data(), n_axis, map.data());
 }
 
+// The SNV tail both entry points share.  reserve_last_rows: every scratch array of n_snv rows and room for as many new rows behind the
+// sample's (a call adds at most one row per SNV row) -- before anything is launched.  launch_last_rows: st->keys_in / idx_in hold the
+// (set position, mm) keys of the source rows; sort, flag the last row of every position, scan, gather them behind the sample's rows.
+int reserve_last_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv)
+{
+    hipStream_t s = st->ctx->stream;
+    HIP_TRY(st->keys.fit(n_snv)); HIP_TRY(st->keys_in.fit(n_snv)); HIP_TRY(st->idx.fit(n_snv)); HIP_TRY(st->idx_in.fit(n_snv));
+    HIP_TRY(st->flags.fit(n_snv)); HIP_TRY(st->pos.fit((size_t)n_snv + 1));
+    size_t t_sort = 0, t_scan = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
+    HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
+    const int rc = grow_temp(st, std::max(t_sort, t_scan));
+    if (rc) return rc;
+    if (sm.cap_rows < sm.n_rows + n_snv) {
+        const size_t want = std::max(sm.n_rows + n_snv, sm.cap_rows * 2);
+        CsRow *grown = nullptr;
+        HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(CsRow)));
+        if (sm.n_rows) HIP_TRY(hipMemcpyAsync(grown, sm.rows, sm.n_rows * sizeof(CsRow), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(isx_wait_stream(s));
+        if (sm.rows) isx_dev_free(sm.rows);
+        sm.rows = grown; sm.cap_rows = want;
+    }
+    return ISX_OK;
+}
+
+template <class Src>
+int launch_last_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv, const Src *d_snv, uint32_t *n_new)
+{
+    hipStream_t s = st->ctx->stream;
+    const dim3 blk(256), grid((n_snv + 255) / 256);
+    size_t tb = st->temp.cap;
+    HIP_TRY(rocprim::radix_sort_pairs(st->temp.p, tb, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
+    hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
+    tb = st->temp.cap;
+    HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_gather_last<Src>, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, d_snv,
+                       sm.rows + sm.n_rows, (uint32_t)(sm.cap_rows - sm.n_rows), st->pos.p + n_snv);
+    HIP_TRY(hipMemcpyAsync(n_new, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
+    return ISX_OK;
+}
+
 // rows (compare rows or pool rows) of a sample whose batches did not arrive in set order: one sort by position
 template <class Row>
 int sort_rows_of(isx_cmpset *st, Row *&rows, size_t n_rows, size_t cap_rows, bool &sorted)
@@ -510,22 +615,8 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     HIP_TRY(st->set_pos0.put(set_pos0, s));
     HIP_TRY(st->jobs.put(jobs, s));
     if (n_snv) {
-        HIP_TRY(st->keys.fit(n_snv)); HIP_TRY(st->keys_in.fit(n_snv)); HIP_TRY(st->idx.fit(n_snv)); HIP_TRY(st->idx_in.fit(n_snv));
-        HIP_TRY(st->flags.fit(n_snv)); HIP_TRY(st->pos.fit((size_t)n_snv + 1));
-        size_t t_sort = 0, t_scan = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
-        HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
-        const int rc = grow_temp(st, std::max(t_sort, t_scan));
+        const int rc = reserve_last_rows(st, sm, n_snv);
         if (rc) return rc;
-        if (sm.cap_rows < sm.n_rows + n_snv) {     // the batch adds at most one row per SNV row
-            const size_t want = std::max(sm.n_rows + n_snv, sm.cap_rows * 2);
-            CsRow *grown = nullptr;
-            HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(CsRow)));
-            if (sm.n_rows) HIP_TRY(hipMemcpyAsync(grown, sm.rows, sm.n_rows * sizeof(CsRow), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(isx_wait_stream(s));
-            if (sm.rows) isx_dev_free(sm.rows);
-            sm.rows = grown; sm.cap_rows = want;
-        }
         if (st->pool_on && sm.cap_prows < sm.n_prows + n_snv) {
             const size_t want = std::max(sm.n_prows + n_snv, sm.cap_prows * 2);
             PoolRow *grown = nullptr;
@@ -555,14 +646,8 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     if (n_snv) {
         const dim3 grid((n_snv + 255) / 256);
         hipLaunchKernelGGL(k_set_keys, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
-        size_t tb = st->temp.cap;
-        HIP_TRY(rocprim::radix_sort_pairs(st->temp.p, tb, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
-        hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
-        tb = st->temp.cap;
-        HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
-        hipLaunchKernelGGL(k_gather_last, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, b->d_snv,
-                           sm.rows + sm.n_rows, (uint32_t)(sm.cap_rows - sm.n_rows), st->pos.p + n_snv);
-        HIP_TRY(hipMemcpyAsync(&n_new, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
+        const int rc = launch_last_rows(st, sm, n_snv, b->d_snv, &n_new);
+        if (rc) return rc;
     }
     // pool rows: the same scheme on keys that leave the cryptic rows out, so a position's last row is its highest-mm row that counts
     uint32_t n_new_pool = 0;
@@ -591,6 +676,164 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     sm.n_rows += std::min<size_t>(n_new, sm.cap_rows - sm.n_rows);
     if (n_new_pool && sm.n_prows && min_sid < sm.max_sid) sm.psorted = false;
     sm.n_prows += std::min<size_t>(n_new_pool, sm.cap_prows - sm.n_prows);
+    sm.max_sid = std::max(sm.max_sid, max_sid);
+    return ISX_OK;
+}
+
+int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, const int32_t *ids, int32_t L, const int32_t *level_mm_values,
+                           const uint8_t *present, const int64_t *off, const uint32_t *positions, const uint32_t *values, int64_t n_snv_in,
+                           const isx_profile_snv *snv, float *device_ms)
+{
+    const std::string who("isx_cmpset_add_profile: ");
+    if (device_ms) *device_ms = 0.f;
+    if (!st || sample < 0 || sample >= ISX_CMPSET_MAX_SAMPLES || n_cscaf <= 0 || !ids || L <= 0 || !level_mm_values || !present || !off ||
+        n_snv_in < 0 || (n_snv_in && !snv)) {
+        isx_set_error(who + "bad argument");
+        return ISX_ERR_ARG;
+    }
+    if (st->pool_on) {
+        isx_set_error(who + "a set with pooling enabled takes resident batches only (its own rows need the class / cryptic columns, the pull needs reads)");
+        return ISX_ERR_STATE;
+    }
+    if (L > ISX_CMPSET_MAX_LEVELS) {
+        isx_set_error(who + "a profile of " + std::to_string(L) + " levels; a set compares at most " + std::to_string(ISX_CMPSET_MAX_LEVELS));
+        return ISX_ERR_CAPACITY;
+    }
+    if (n_snv_in > (int64_t)0x7FFFFFFFll) { isx_set_error(who + "more SNV rows than one call holds"); return ISX_ERR_CAPACITY; }
+    const std::vector<int32_t> mmv(level_mm_values, level_mm_values + L);
+    for (int k = 0; k < L; k++)
+        if (mmv[(size_t)k] < 0 || mmv[(size_t)k] > 65535 || (k && mmv[(size_t)k] <= mmv[(size_t)k - 1])) {
+            isx_set_error(who + "level_mm_values must ascend strictly within 0..65535");
+            return ISX_ERR_ARG;
+        }
+    const bool fresh = (size_t)sample >= st->samples.size() || st->samples[(size_t)sample].mm.empty();
+    if (!fresh && st->samples[(size_t)sample].mm != mmv) {
+        isx_set_error(who + "this call's level_mm_values differ from those of the sample's earlier calls");
+        return ISX_ERR_ARG;
+    }
+    // the call's scaffolds
+    std::vector<uint8_t> seen((size_t)st->n_scaf, 0);
+    std::vector<int64_t> set_pos0((size_t)n_cscaf, -1), sub_len;
+    std::vector<int32_t> sub_scaf;                  // the call's scaffolds the set names
+    int32_t min_sid = st->n_scaf, max_sid = -1;
+    for (int i = 0; i < n_cscaf; i++) {
+        const int32_t sid = ids[i];
+        if (sid == -1) continue;
+        if (sid < 0 || sid >= st->n_scaf) { isx_set_error(who + "set_scaffold_ids[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
+        if (seen[(size_t)sid] || (!fresh && st->samples[(size_t)sample].have[(size_t)sid])) {
+            isx_set_error(who + "scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was added before");
+            return ISX_ERR_STATE;
+        }
+        seen[(size_t)sid] = 1;
+        set_pos0[(size_t)i] = st->spos[(size_t)sid];
+        sub_scaf.push_back(i);
+        sub_len.push_back(st->len[(size_t)sid]);
+        min_sid = std::min(min_sid, sid); max_sid = std::max(max_sid, sid);
+    }
+    // the covT series
+    const int64_t n_series = (int64_t)n_cscaf * L;
+    if (off[0] != 0) { isx_set_error(who + "entry_offsets must start at 0"); return ISX_ERR_ARG; }
+    for (int64_t q = 0; q < n_series; q++)
+        if (off[q + 1] < off[q]) { isx_set_error(who + "entry_offsets must not descend"); return ISX_ERR_ARG; }
+    const int64_t n_entries = off[n_series];
+    if (n_entries && (!positions || !values)) { isx_set_error(who + "bad argument"); return ISX_ERR_ARG; }
+    for (int i = 0; i < n_cscaf; i++)
+        for (int k = 0; k < L; k++) {
+            const int64_t q = (int64_t)i * L + k, b = off[q], e = off[q + 1];
+            if (!present[q] && e != b) {
+                isx_set_error(who + "scaffold " + std::to_string(i) + " has entries at a level that is no key of its covT");
+                return ISX_ERR_ARG;
+            }
+            if (ids[i] < 0) continue;
+            const int64_t len = st->len[(size_t)ids[i]];
+            for (int64_t x = b; x < e; x++)
+                if ((int64_t)positions[x] >= len || (x > b && positions[x] <= positions[x - 1])) {
+                    isx_set_error(who + "the positions of scaffold " + std::to_string(i) + ", level " + std::to_string(k) +
+                                  " must ascend strictly below the scaffold's length");
+                    return ISX_ERR_ARG;
+                }
+        }
+    // the SNV rows
+    const uint32_t n_snv = (uint32_t)n_snv_in;
+    for (uint32_t r = 0; r < n_snv; r++) {
+        const isx_profile_snv &x = snv[r];
+        const bool ok = x.scaffold >= 0 && x.scaffold < n_cscaf && x.mm >= 0 && x.mm <= 65535 && x.con_base <= 3 && x.var_base <= 3 &&
+                        x.ref_base <= 4 && (ids[x.scaffold] < 0 || (int64_t)x.position < st->len[(size_t)ids[x.scaffold]]);
+        if (!ok) {
+            isx_set_error(who + "SNV row " + std::to_string(r) + ": scaffold index, position, mm or a base code out of range");
+            return ISX_ERR_ARG;
+        }
+    }
+    if (sub_scaf.empty()) return ISX_OK;            // nothing of this call is in the set
+    // the tiles: the set's tile geometry over the call's scaffolds only
+    const int64_t n_tiles = isx_cmpset_tiles((int32_t)sub_len.size(), sub_len.data(), PROF_TILE_WORDS, nullptr);
+    if (n_tiles < 0) return (int)n_tiles;
+    if (n_tiles > 0x7FFFFFFFll) { isx_set_error(who + "too many tiles for one launch"); return ISX_ERR_CAPACITY; }
+    std::vector<isx_cmpset_tile> sub_tiles((size_t)n_tiles);
+    (void)isx_cmpset_tiles((int32_t)sub_len.size(), sub_len.data(), PROF_TILE_WORDS, sub_tiles.data());
+    std::vector<int64_t> sub_off(sub_len.size() + 1);
+    (void)isx_cmpset_layout((int32_t)sub_len.size(), sub_len.data(), sub_off.data());
+    std::vector<ProfTile> tiles((size_t)n_tiles);
+    for (int64_t q = 0; q < n_tiles; q++) {
+        const isx_cmpset_tile &u = sub_tiles[(size_t)q];
+        const int32_t i = sub_scaf[(size_t)u.scaffold], sid = ids[i];
+        const int64_t w_in = u.word0 - sub_off[(size_t)u.scaffold];
+        tiles[(size_t)q] = {st->woff[(size_t)sid] + w_in, u.n_words, i, (uint32_t)(w_in * 64), (uint32_t)st->len[(size_t)sid]};
+    }
+
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    hipStream_t s = st->ctx->stream;
+    if ((size_t)sample >= st->samples.size()) st->samples.resize((size_t)sample + 1);
+    Sample &sm = st->samples[(size_t)sample];
+    if (sm.mm.empty()) {                            // the sample's first call fixes its levels
+        if (sm.planes) isx_dev_free(sm.planes);
+        sm.planes = nullptr;
+        HIP_TRY(isx_raw_dev_malloc(&sm.planes, (size_t)L * (size_t)st->n_words * 8));
+        HIP_TRY(hipMemsetAsync(sm.planes, 0, (size_t)L * (size_t)st->n_words * 8, s));
+        sm.have.assign((size_t)st->n_scaf, 0);
+        sm.present.assign((size_t)st->n_scaf * L, 0);
+    }
+    st->compared = false;
+    st->clustered = false;
+    st->pooled = false;
+    // scratch and uploads, all sized before anything is launched
+    HIP_TRY(st->pf_off.fit((size_t)n_series + 1)); HIP_TRY(st->pf_pos.fit((size_t)n_entries)); HIP_TRY(st->pf_val.fit((size_t)n_entries));
+    HIP_TRY(st->pf_snv.fit(n_snv));
+    if (n_snv) {
+        const int rc = reserve_last_rows(st, sm, n_snv);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(st->pf_off.p, off, ((size_t)n_series + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_entries) {
+        HIP_TRY(hipMemcpyAsync(st->pf_pos.p, positions, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st->pf_val.p, values, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
+    }
+    if (n_snv) HIP_TRY(hipMemcpyAsync(st->pf_snv.p, snv, (size_t)n_snv * sizeof(isx_profile_snv), hipMemcpyHostToDevice, s));
+    HIP_TRY(st->pf_tiles.put(tiles, s));
+    HIP_TRY(st->set_pos0.put(set_pos0, s));
+    HIP_TRY(hipEventRecord(st->ev[0], s));
+    hipLaunchKernelGGL(k_profile_planes, dim3((unsigned)n_tiles), dim3(256), 0, s, st->pf_tiles.p, st->pf_off.p, (int)L, st->pf_pos.p,
+                       st->pf_val.p, (uint32_t)st->min_cov, sm.planes, st->n_words);
+    uint32_t n_new = 0;
+    if (n_snv) {
+        hipLaunchKernelGGL(k_profile_keys, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, n_snv, st->set_pos0.p, (int)n_cscaf,
+                           st->keys_in.p, st->idx_in.p);
+        const int rc = launch_last_rows(st, sm, n_snv, st->pf_snv.p, &n_new);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipEventRecord(st->ev[1], s));
+    HIP_TRY(isx_wait_stream(s));
+    HIP_TRY(hipGetLastError());
+    if (device_ms) (void)hipEventElapsedTime(device_ms, st->ev[0], st->ev[1]);
+    // only now is the call part of the sample
+    if (sm.mm.empty()) sm.mm = mmv;
+    for (int i = 0; i < n_cscaf; i++) {
+        if (ids[i] < 0) continue;
+        sm.have[(size_t)ids[i]] = 1;
+        for (int k = 0; k < L; k++) sm.present[(size_t)ids[i] * L + k] = present[(size_t)i * L + k] ? 1 : 0;
+    }
+    if (n_new && sm.n_rows && min_sid < sm.max_sid) sm.sorted = false;
+    sm.n_rows += std::min<size_t>(n_new, sm.cap_rows - sm.n_rows);
     sm.max_sid = std::max(sm.max_sid, max_sid);
     return ISX_OK;
 }
