@@ -1191,6 +1191,24 @@ int isx_bam_r2m(const isx_bam *bam, int32_t ref, int64_t *n, int64_t *name_bytes
 int isx_bam_drop_names(isx_bam *bam);                   /* frees the read names (no filter / set_r2m call may follow) */
 /* per reference: records in the file, pairs that passed the filter (the reference's s2p, profile_controller.py:441) */
 int isx_bam_ref_counts(const isx_bam *bam, int64_t *reads, int64_t *filtered_pairs);
+/* The read report of the last isx_bam_filter: per scaffold what filter_scaff2pair2info tabulates (filter_reads.py:201-268;
+ * mapping_info.tsv is made of these rows).  Host only, a sweep of its own over the pair table: a caller that never asks pays
+ * nothing.  Counts are exact; the means of the reference's table are sum / pass_pairing_filter. */
+typedef struct isx_read_report_row_s {
+    int64_t unfiltered_reads, unfiltered_pairs, unfiltered_singletons, unfiltered_priority_reads;  /* paired_read_filter :487-500 */
+    int64_t pass_pairing_filter, pass_min_read_ani, pass_max_insert, pass_min_insert, pass_min_mapq; /* update_tallys :363-374 */
+    int64_t filtered_pairs, filtered_singletons, filtered_priority_reads;                            /* :377-385 */
+    int64_t sum_mismatches, sum_insert_distance, sum_mapq, sum_pair_length;  /* info[0..3] of every entry that went through the pairing filter */
+    double  sum_pid;            /* sum of 1 - nm / length over the same entries, in table order */
+    double  median_insert;      /* np.median of info[1] over the same entries (-1 / -2 included); NaN when there are none */
+} isx_read_report_row;
+/* one row per reference of the header, as the last isx_bam_filter left the table; rows == NULL asks for *n only.  Needs a filter
+ * run (else ISX_ERR_STATE); works after isx_bam_drop_names and isx_bam_drop_refs.  A reference outside isx_bam_set_wanted_refs,
+ * or not owned by this share (isx_bam_scan_part), gets a zero row with a NaN median.  The rows do not depend on the thread count. */
+int isx_bam_read_report(const isx_bam *bam, isx_read_report_row *rows, int32_t cap, int32_t *n);
+/* the pairs of these references no longer pass (filter_fasta dropped their scaffolds): totals (filtered_pairs, filtered_bases,
+ * filtered_singletons, max_mm), isx_bam_ref_counts and isx_bam_mm_levels are recomputed over what is left */
+int isx_bam_drop_refs(isx_bam *bam, const int32_t *refs, int32_t n);
 /* overlap resolution + expansion of the given references (ascending ids = file order), laid end to end (the batch's
  * flat space); results stay in the handle until the next expand (isx_bam_copy / isx_bam_view) */
 int isx_bam_expand_refs(isx_bam *bam, const isx_bam_params *p, const int32_t *refs, int32_t n_refs, isx_bam_info *info);

@@ -171,6 +171,12 @@ CLUSTER_OK, CLUSTER_NO_OVERLAP, CLUSTER_MISSING_PAIR, CLUSTER_EMPTY = 0, 1, 2, 3
 CLUSTER_STATUS_DT = np.dtype([("status", "<i4"), ("n_points", "<i4")])                  # isx_cluster_status
 GENOME_PAIR_DT = np.dtype([("tcb", "<i8"), ("w", "<f8"), ("n_rows", "<i4"), ("pad", "<i4")])    # isx_genome_pair
 assert GENOME_PAIR_DT.itemsize == 24
+READ_REPORT_DT = np.dtype([(n, "<i8") for n in ("unfiltered_reads", "unfiltered_pairs", "unfiltered_singletons", "unfiltered_priority_reads",
+                                               "pass_pairing_filter", "pass_min_read_ani", "pass_max_insert", "pass_min_insert", "pass_min_mapq",
+                                               "filtered_pairs", "filtered_singletons", "filtered_priority_reads",
+                                               "sum_mismatches", "sum_insert_distance", "sum_mapq", "sum_pair_length")]
+                          + [("sum_pid", "<f8"), ("median_insert", "<f8")])          # isx_read_report_row
+assert READ_REPORT_DT.itemsize == 144
 
 
 GENE_DT = np.dtype([("start", "<i8"), ("end", "<i8"), ("seq_off", "<i8"), ("strand", "<i4"), ("pad", "<i4")])
@@ -204,7 +210,7 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_pack_ref_planes", "isx_planes_from_segs", "isx_pack_read_planes", "isx_pipe_submit_planes", "isx_pipe_stage_planes", "isx_encode_planes", "isx_encode_planes_mm", "isx_pipe_set_reference_budget", "isx_host_register", "isx_host_unregister",
            "isx_bgzf_index", "isx_bgzf_inflate_device", "isx_bgzf_inflate_host", "isx_bgzf_inflate_fast",
            "isx_bam_open", "isx_bam_close", "isx_bam_close_wait", "isx_bam_set_threads", "isx_bam_ref", "isx_bam_set_priority_reads", "isx_bam_scan", "isx_bam_scan_part",
-           "isx_bam_insert_sizes", "isx_bam_set_wanted_refs", "isx_bam_pair_keys", "isx_bam_set_cross_names", "isx_bam_filter_insert_sizes", "isx_bam_filter", "isx_bam_set_r2m", "isx_bam_r2m", "isx_bam_drop_names", "isx_bam_batch_pair_names", "isx_bam_set_mm_cap", "isx_bam_mm_levels", "isx_bam_set_mm_levels", "isx_bam_ref_counts",
+           "isx_bam_insert_sizes", "isx_bam_set_wanted_refs", "isx_bam_pair_keys", "isx_bam_set_cross_names", "isx_bam_filter_insert_sizes", "isx_bam_filter", "isx_bam_set_r2m", "isx_bam_r2m", "isx_bam_drop_names", "isx_bam_batch_pair_names", "isx_bam_set_mm_cap", "isx_bam_mm_levels", "isx_bam_set_mm_levels", "isx_bam_ref_counts", "isx_bam_read_report", "isx_bam_drop_refs",
            "isx_bam_expand_refs", "isx_bam_segment_refs", "isx_bam_copy_segs", "isx_bam_copy_read_planes", "isx_bam_expand_region", "isx_bam_expand", "isx_bam_copy", "isx_bam_view"]
 
 _lib = None
@@ -346,6 +352,8 @@ def load():
     lib.isx_bam_mm_levels.argtypes = [vp, vp, i32, vp]
     lib.isx_bam_set_mm_levels.argtypes = [vp, vp, i32]
     lib.isx_bam_ref_counts.argtypes = [vp, vp, vp]
+    lib.isx_bam_read_report.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    lib.isx_bam_drop_refs.argtypes = [vp, vp, i32]
     lib.isx_bam_expand_region.argtypes = [vp, C.POINTER(BamParams), i32, i64, i64, C.POINTER(BamInfo)]
     lib.isx_bam_expand_refs.argtypes = [vp, C.POINTER(BamParams), vp, i32, C.POINTER(BamInfo)]
     lib.isx_bam_segment_refs.argtypes = [vp, C.POINTER(BamParams), vp, i32, C.POINTER(BamInfo), C.POINTER(i64)]

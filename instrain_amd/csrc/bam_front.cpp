@@ -42,6 +42,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <condition_variable>
 #include <mutex>
@@ -598,6 +599,10 @@ struct isx_bam {
     std::vector<uvec<uint8_t>> seg_cache;
     std::vector<std::vector<uint64_t>> seg_cache_rec;
     std::vector<int64_t> ref_filtered_pairs, ref_reads;
+    // what the last isx_bam_filter ran with: isx_bam_read_report judges every criterion of evaluate_pair on its own from these
+    bool filter_ran = false;
+    isx_bam_params filter_params{};
+    double filter_max_insert = 0;
     // ---- results of the last expand ----
     std::unique_ptr<isx_obs[]> obs;
     std::unique_ptr<uint32_t[]> pair;
@@ -1910,6 +1915,7 @@ int isx_bam_filter(isx_bam *bam, const isx_bam_params *p, double median_insert, 
     T.max_mm = p->skip_mm ? 0 : (int32_t)max_mm;
     B.totals = T;
     B.filtered = true;
+    B.filter_params = *p; B.filter_max_insert = max_insert; B.filter_ran = true;       // for isx_bam_read_report / isx_bam_drop_refs
     if (info) *info = T;
     return ISX_OK;
 }
@@ -2041,6 +2047,134 @@ int isx_bam_ref_counts(const isx_bam *bam, int64_t *reads, int64_t *filtered_pai
         if (reads) reads[t] = bam->ref_reads[t];
         if (filtered_pairs) filtered_pairs[t] = bam->ref_filtered_pairs.size() == n ? bam->ref_filtered_pairs[t] : 0;
     }
+    return ISX_OK;
+}
+
+// ---- the read report: filter_scaff2pair2info's per-scaffold table (filter_reads.py:201-268) for the last isx_bam_filter ----
+// A sweep of its own over the pair table (the filter keeps whole-file tallies only and is not touched).  The table is cut into
+// pieces that never cross a reference and are at most REPORT_BLOCK entries long -- the cut follows from the table alone, never
+// from the pool, so the rows are the same bytes on any number of threads: integer tallies add exactly, sum_pid is summed in
+// table order inside a piece and the pieces of a reference are added in table order.  The medians are one nth_element per
+// reference on its gathered inserts, references spread over the pool.
+int isx_bam_read_report(const isx_bam *bam, isx_read_report_row *rows, int32_t cap, int32_t *n)
+{
+    if (!bam || !n || cap < 0) { isx_set_error("isx_bam_read_report: bad argument"); return ISX_ERR_ARG; }
+    const isx_bam &B = *bam;
+    if (!B.filter_ran) { isx_set_error("isx_bam_read_report: run isx_bam_filter first (the report describes a filter run)"); return ISX_ERR_STATE; }
+    const size_t n_ref = B.ref_name.size();
+    *n = (int32_t)n_ref;
+    if (!rows) return ISX_OK;
+    if ((size_t)cap < n_ref) { isx_set_error("isx_bam_read_report: one row per reference of the header is needed"); return ISX_ERR_ARG; }
+    // the unfiltered tallies are taken over what the scan found (all_reads rewrites merged entries in place, paired_read_filter
+    // counts i[4] before it merges, :493-500)
+    const std::vector<PairInfo, NoInitAlloc<PairInfo>> &scan = B.pairs_scan.empty() ? B.pairs : B.pairs_scan;
+    const isx_bam_params &P = B.filter_params;
+    const double max_insert = B.filter_max_insert;
+    constexpr uint64_t REPORT_BLOCK = 65536;
+    std::vector<uint64_t> piece_lo;
+    std::vector<uint32_t> piece_ref, ref_piece0(n_ref + 1, 0);
+    for (size_t t = 0; t < n_ref; t++) {
+        ref_piece0[t] = (uint32_t)piece_lo.size();
+        if (!B.ref_wanted.empty() && !B.ref_wanted[t]) continue;           // does not exist for the filter: a zero row
+        for (uint64_t lo = B.ref_pair0[t]; lo < B.ref_pair0[t + 1]; lo += REPORT_BLOCK) { piece_lo.push_back(lo); piece_ref.push_back((uint32_t)t); }
+    }
+    ref_piece0[n_ref] = (uint32_t)piece_lo.size();
+    isx_read_report_row zero;
+    memset(&zero, 0, sizeof zero);
+    zero.median_insert = std::numeric_limits<double>::quiet_NaN();
+    std::vector<isx_read_report_row> part(piece_lo.size(), zero);
+    isxenc::HostPool &pool = pool_of(const_cast<isx_bam &>(B));
+    const bool timing = getenv("ISX_BAM_TIMING") != nullptr;       // tuning aid: stage times on stderr (no effect on results)
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = now();
+    pool.run((int)piece_lo.size(), [&](int k) {
+        isx_read_report_row &r = part[(size_t)k];
+        const uint64_t hi = std::min<uint64_t>(piece_lo[(size_t)k] + REPORT_BLOCK, B.ref_pair0[(size_t)piece_ref[(size_t)k] + 1]);
+        for (uint64_t j = piece_lo[(size_t)k]; j < hi; j++) {
+            const PairInfo &s = scan[(size_t)j];
+            if (s.reads == 0) continue;
+            const bool prio = !B.priority.empty() && B.priority[(size_t)j];
+            r.unfiltered_reads += s.reads; r.unfiltered_pairs += s.reads == 2; r.unfiltered_singletons += s.reads == 1;
+            r.unfiltered_priority_reads += prio;
+            const PairInfo &e = B.pairs[(size_t)j];
+            if (!e.in_filter) continue;
+            r.pass_pairing_filter++;
+            const double pid = 1 - ((double)e.nm / (double)e.length);      // evaluate_pair :406-424
+            const bool ani = pid > P.min_read_ani, mapq = e.mapq > P.min_mapq;
+            bool ins_lo = true, ins_hi = true;
+            if (e.reads == 2 && e.insert != -1) { ins_lo = (double)e.insert > (double)P.min_insert; ins_hi = (double)e.insert < max_insert; }
+            r.pass_min_read_ani += ani; r.pass_max_insert += ins_hi; r.pass_min_insert += ins_lo; r.pass_min_mapq += mapq;
+            if (ani && mapq && ins_lo && ins_hi) { r.filtered_pairs++; r.filtered_singletons += e.reads == 1; r.filtered_priority_reads += prio; }
+            r.sum_mismatches += e.nm; r.sum_insert_distance += e.insert; r.sum_mapq += e.mapq; r.sum_pair_length += e.length;
+            r.sum_pid += pid;
+        }
+    });
+    const double t_sweep = now();
+    pool.run((int)n_ref, [&](int ti) {
+        const size_t t = (size_t)ti;
+        isx_read_report_row r = zero;
+        for (uint32_t k = ref_piece0[t]; k < ref_piece0[t + 1]; k++) {
+            const isx_read_report_row &q = part[k];
+            r.unfiltered_reads += q.unfiltered_reads; r.unfiltered_pairs += q.unfiltered_pairs; r.unfiltered_singletons += q.unfiltered_singletons;
+            r.unfiltered_priority_reads += q.unfiltered_priority_reads;
+            r.pass_pairing_filter += q.pass_pairing_filter; r.pass_min_read_ani += q.pass_min_read_ani; r.pass_max_insert += q.pass_max_insert;
+            r.pass_min_insert += q.pass_min_insert; r.pass_min_mapq += q.pass_min_mapq;
+            r.filtered_pairs += q.filtered_pairs; r.filtered_singletons += q.filtered_singletons; r.filtered_priority_reads += q.filtered_priority_reads;
+            r.sum_mismatches += q.sum_mismatches; r.sum_insert_distance += q.sum_insert_distance; r.sum_mapq += q.sum_mapq;
+            r.sum_pair_length += q.sum_pair_length;
+            r.sum_pid += q.sum_pid;
+        }
+        if (r.pass_pairing_filter > 0) {                                    // np.median of info[1] (selection, not a full sort)
+            std::vector<int64_t> ins;
+            ins.reserve((size_t)r.pass_pairing_filter);
+            for (uint64_t j = B.ref_pair0[t]; j < B.ref_pair0[t + 1]; j++) {
+                const PairInfo &e = B.pairs[(size_t)j];
+                if (e.in_filter) ins.push_back(e.insert);
+            }
+            const size_t m = ins.size();
+            std::nth_element(ins.begin(), ins.begin() + (ptrdiff_t)(m / 2), ins.end());
+            const double hi = (double)ins[m / 2];
+            r.median_insert = (m & 1) ? hi : ((double)*std::max_element(ins.begin(), ins.begin() + (ptrdiff_t)(m / 2)) + hi) / 2.0;
+        }
+        rows[t] = r;
+    });
+    if (timing) fprintf(stderr, "isx_bam_read_report: sweep %.2f ms (%zu pieces), per-reference sums + medians %.2f ms\n", t_sweep - t_begin, piece_lo.size(), now() - t_sweep);
+    return ISX_OK;
+}
+
+// filter_fasta dropped these references' scaffolds (profile/fasta.py:87-136): their pairs no longer pass, and what the handle
+// says about the kept pairs -- the totals' filtered_* and max_mm, isx_bam_ref_counts, isx_bam_mm_levels -- is taken again over
+// what is left.  isx_bam_read_report is not changed: it describes the filter run, not what was kept afterwards.
+int isx_bam_drop_refs(isx_bam *bam, const int32_t *refs, int32_t n)
+{
+    if (!bam || n < 0 || (n && !refs)) { isx_set_error("isx_bam_drop_refs: bad argument"); return ISX_ERR_ARG; }
+    isx_bam &B = *bam;
+    if (!B.filtered) { isx_set_error("isx_bam_drop_refs: filter first"); return ISX_ERR_STATE; }
+    const size_t n_ref = B.ref_name.size();
+    for (int32_t i = 0; i < n; i++)
+        if (refs[i] < 0 || (size_t)refs[i] >= n_ref) { isx_set_error("isx_bam_drop_refs: reference id out of range"); return ISX_ERR_ARG; }
+    if (B.ref_filtered_pairs.size() != n_ref) B.ref_filtered_pairs.assign(n_ref, 0);
+    for (int32_t i = 0; i < n; i++) {
+        const size_t t = (size_t)refs[i];
+        for (uint64_t j = B.ref_pair0[t]; j < B.ref_pair0[t + 1]; j++) B.pairs[(size_t)j].pass = false;
+        B.ref_filtered_pairs[t] = 0;
+    }
+    struct Tally { int64_t f_pairs = 0, f_single = 0, f_bases = 0, max_mm = 0; };
+    std::vector<Tally> tl(n_ref);
+    pool_of(B).run((int)n_ref, [&](int ti) {
+        Tally &t = tl[(size_t)ti];
+        for (uint64_t j = B.ref_pair0[(size_t)ti]; j < B.ref_pair0[(size_t)ti + 1]; j++) {
+            const PairInfo &e = B.pairs[(size_t)j];
+            if (!e.pass || e.reads == 0) continue;
+            t.f_pairs++; t.f_bases += e.length; t.f_single += e.reads == 1;
+            if (e.mm > t.max_mm) t.max_mm = e.mm;
+        }
+    });
+    isx_bam_info &T = B.totals;
+    T.filtered_pairs = T.filtered_bases = T.filtered_singletons = 0;
+    int64_t max_mm = 0;
+    for (const Tally &t : tl) { T.filtered_pairs += t.f_pairs; T.filtered_bases += t.f_bases; T.filtered_singletons += t.f_single; max_mm = std::max(max_mm, t.max_mm); }
+    T.max_mm = (B.filter_ran && B.filter_params.skip_mm) ? 0 : (int32_t)max_mm;
     return ISX_OK;
 }
 

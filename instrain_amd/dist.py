@@ -196,6 +196,26 @@ def resolve_cross_names(bf, rank, world, device=None):
     return int(mine.sum())
 
 
+def gather_read_report(bf, sharded, device=None):
+    """The read report of the whole file on every rank (engine.BamFile.read_report after the final filter run).  sharded: every
+    rank scanned its share, so it owns whole references and the shares' per-scaffold rows are disjoint -- the rows of the owned
+    references (those with records in this handle) are all-gathered with their index, one small structured array like CROSS_DT;
+    otherwise every rank scanned the whole file and already holds every row.  Collective when sharded: every rank calls it."""
+    from ._lib import READ_REPORT_DT
+    rows = bf.read_report()
+    if not sharded:
+        return rows
+    reads, _ = bf.ref_counts()
+    own = np.flatnonzero(reads > 0)
+    rec = np.zeros(len(own), dtype=np.dtype([("tid", "<i8"), ("row", READ_REPORT_DT)]))
+    rec["tid"], rec["row"] = own, rows[own]
+    rec = all_gather_concat(rec, device)
+    out = np.zeros(len(rows), dtype=READ_REPORT_DT)
+    out["median_insert"] = np.nan
+    out[rec["tid"]] = rec["row"]
+    return out
+
+
 def profile_bam_sharded(bam, s2s, null_model, rank, world, gather=True, device=None, **kwargs):
     """Scaffolds of ONE sorted BAM over `world` ranks.
     paired_only (the default): every rank scans only its SHARE of the file (isx_bam_scan_part) and owns the scaffolds whose
@@ -204,12 +224,22 @@ def profile_bam_sharded(bam, s2s, null_model, rank, world, gather=True, device=N
     all_gather of the shares' insert sizes (all_gather_concat).  Other pairing filters look read names up across all
     scaffolds: there every rank scans the whole file and the scaffolds are dealt by LPT (shard_scaffolds).
     Each rank profiles its scaffolds through profile_bam; SNV / linkage / per-scaffold summary tables are gathered on rank 0
-    (gather_tables).  Returns (splits of this rank, gathered tables on rank 0 | None, this rank's load)."""
+    (gather_tables).  With `read_tables` / `min_scaffold_reads` / `min_genome_coverage` / `database_mode` (profile_bam's keywords) the
+    read report of the WHOLE file is made first (gather_read_report: a collective, every rank calls), filter_scaffolds runs on it
+    identically on every rank before the scaffolds are dealt, and rank 0 gets the table under the key `read_report`.
+    Returns (splits of this rank, gathered tables on rank 0 | None, this rank's load)."""
     import pandas as pd
     from . import engine
     from ._lib import LD_DT, SCAFFOLD_LEVEL_DT, SNV_DT
     from .profile import profile_utilities as pu
-    fkw = pu.read_filter_flags(kwargs)
+    opt = pu.profile_options(kwargs)
+    fkw = opt.filter                                # (database_mode already applied)
+    # the read report and the scaffold filters that read it describe the whole file: made here from every share's rows, the same
+    # on every rank, and handed to profile_bam (a share alone cannot tell a genome's coverage)
+    want_report = opt.read_tables is not None or bool(opt.min_scaffold_reads or opt.min_genome_coverage)
+    if opt.min_genome_coverage and kwargs.get('stb') is None:
+        raise ValueError("If you adjust the minimum genome coverage, you need to provide an .stb!")
+    rdb = None
     sharded_scan = world > 1 and kwargs.get('scan', 'sharded') == 'sharded'
     bf = engine.BamFile(bam, threads=int(kwargs.get('host_threads', 0)))
     try:
@@ -251,12 +281,40 @@ def profile_bam_sharded(bam, s2s, null_model, rank, world, gather=True, device=N
             owned = all_gather_concat((reads > 0).astype(np.uint8), device).reshape(world, -1).sum(axis=0)
             mine = [t for t in usable if reads[t] > 0 or (owned[t] == 0 and t % world == rank)]
             extra = dict(scan_part=part, median_insert=median)
+            if want_report:                         # the final filter run: profile_bam is told that it has happened
+                if kwargs.get('priority_reads'):
+                    bf.set_priority_reads(kwargs['priority_reads'])
+                bf.filter(median_insert=median, **fkw)
         else:
             bf.scan()
+            if want_report and kwargs.get('priority_reads'):
+                bf.set_priority_reads(kwargs['priority_reads'])
             bf.filter(**fkw)
+        usable_kept = usable
+        if want_report:
+            from .profile import filter_reads, genome_utilities
+            names = [n for n, _, _ in refs]
+            rdb = filter_reads.mapping_info(gather_read_report(bf, sharded_scan, device), names, filter_refs or None)
+            s2p = rdb.set_index('scaffold')['filtered_pairs'].to_dict()
+            stb = genome_utilities.parse_stb(kwargs['stb']) if kwargs.get('stb') is not None else None
+            kept, removed = filter_reads.filter_scaffolds([names[t] for t in usable], s2p, {n: ln for n, ln, _ in refs},
+                                                          float(rdb.loc[0, 'mean_pair_length']), min_scaffold_reads=opt.min_scaffold_reads,
+                                                          min_genome_coverage=opt.min_genome_coverage, stb=stb)
+            if removed:
+                kept = set(kept)
+                usable_kept = [t for t in usable if names[t] in kept]
+                bf.drop_refs([t for t in usable if names[t] not in kept])
+                if sharded_scan:
+                    keep_tids = set(usable_kept)
+                    mine = [t for t in mine if t in keep_tids]
+            # the handle is filtered and has forgotten the removed scaffolds: profile_bam takes the finished table instead of doing both again
+            extra['read_report_done'] = (rdb, removed)
+            if opt.read_tables is not None:         # (a rank that is left without a scaffold never gets to profile_bam)
+                opt.read_tables['mapping_info'], opt.read_tables['scaffolds_removed'] = rdb, removed
+        if not sharded_scan:
             _, pairs = bf.ref_counts()
-            shards = shard_scaffolds([pairs[i] for i in usable], [refs[i][1] for i in usable], world)
-            mine = [usable[j] for j in shards[rank]]
+            shards = shard_scaffolds([pairs[i] for i in usable_kept], [refs[i][1] for i in usable_kept], world)
+            mine = [usable_kept[j] for j in shards[rank]]
         W = int(kwargs.get('window_length', 10000))
         rows = [(refs[t][0], i, s, e) for t in mine for i, (s, e) in enumerate(pu.iterate_splits(refs[t][1], W))]
         fdb = pd.DataFrame(rows, columns=["scaffold", "split_number", "start", "end"])
@@ -301,4 +359,7 @@ def profile_bam_sharded(bam, s2s, null_model, rank, world, gather=True, device=N
     tables = {"snv": np.concatenate(snv_parts) if snv_parts else np.zeros(0, snv_dt),
               "ld": np.concatenate(ld_parts) if ld_parts else np.zeros(0, ld_dt),
               "summary": np.concatenate(sm_parts) if sm_parts else np.zeros(0, sm_dt)}
-    return splits, gather_tables(tables, dst=0, device=device), load
+    gathered = gather_tables(tables, dst=0, device=device)
+    if gathered is not None and rdb is not None:
+        gathered["read_report"] = rdb               # mapping_info of the whole file: every rank holds it, nothing travels
+    return splits, gathered, load

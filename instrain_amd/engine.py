@@ -1197,6 +1197,7 @@ class BamFile:
         self.h = h
         self.info = None
         self._refs = None
+        self._part = None
         if threads:
             check(self.lib.isx_bam_set_threads(self.h, int(threads)))
 
@@ -1219,6 +1220,7 @@ class BamFile:
         """pass 1: pair tables of every reference (get_paired_reads); part = (i, n): only share i of n of the file -- the
         handle then owns the references whose first read lies in that share (ref_counts() is zero for the others)"""
         info = BamInfo()
+        self._part = part
         if part is None:
             check(self.lib.isx_bam_scan(self.h, C.byref(info)))
         else:
@@ -1332,6 +1334,24 @@ class BamFile:
         reads, pairs = np.zeros(n, np.int64), np.zeros(n, np.int64)
         check(self.lib.isx_bam_ref_counts(self.h, reads.ctypes.data, pairs.ctypes.data))
         return reads, pairs
+
+    def read_report(self):
+        """the read report of the last filter(): one _lib.READ_REPORT_DT row per reference of the header (isx_bam_read_report) --
+        what profile.filter_reads.mapping_info makes mapping_info.tsv of.  Host only; a zero row with a NaN median for a reference
+        outside set_wanted_refs() or not owned by this handle's share of the file."""
+        n = C.c_int32(0)
+        check(self.lib.isx_bam_read_report(self.h, None, 0, C.byref(n)))
+        rows = np.zeros(n.value, dtype=_lib.READ_REPORT_DT)
+        if n.value:
+            check(self.lib.isx_bam_read_report(self.h, rows.ctypes.data, n.value, C.byref(n)))
+        return rows
+
+    def drop_refs(self, tids):
+        """the pairs of these references no longer pass (filter_fasta dropped their scaffolds): info's filtered_* and max_mm,
+        ref_counts() and mm_levels() are taken over what is left (isx_bam_drop_refs); read_report() still describes the filter"""
+        r = np.ascontiguousarray(tids, dtype=np.int32)
+        check(self.lib.isx_bam_drop_refs(self.h, r.ctypes.data if len(r) else None, len(r)))
+        return self.scan(part=self._part)            # a scanned handle only hands its totals back
 
     def _results(self, info, copy):
         bounds = np.empty(info.n_splits + 1, dtype=np.int64)

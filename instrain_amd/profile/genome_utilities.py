@@ -74,8 +74,7 @@ class GenomeTables:
     per-genome coverage distribution; genome_info() makes the reference's table.
 
     iRep / iRep_GC_corrected are NaN until set_irep() brought the finished rows of an engine.IRep built on irep_scaffolds().
-    Not produced: the reads_* / filtered_read_pair_count columns of the reference's table (they come from a per-scaffold
-    mapping_info, which this package does not make yet)."""
+    The reads_* / filtered_read_pair_count columns are there once set_mapping_info() brought the run's mapping_info."""
 
     def __init__(self, stb, scaffold2length, mask_edges=100):
         self.stb = parse_stb(stb)
@@ -98,6 +97,7 @@ class GenomeTables:
         self._acc = None                    # [G, n_levels] GENOME_COV_DT
         self._hist = None                   # [G, n_levels, bins] int64
         self._irep = None                   # [G] IREP_ROW_DT (set_irep) or None: both iRep columns NaN
+        self._rr = None                     # per genome: the reads_* columns (set_mapping_info) or None: genome_info has none
 
     def batch_genomes(self, names):
         """-> (genome id of every scaffold for engine.Batch.genome_coverage, -1 = none; the genomes those ids stand for).
@@ -130,6 +130,13 @@ class GenomeTables:
         if rows.shape != (len(self.genomes),):
             raise ValueError("GenomeTables.set_irep: one row per genome expected")
         self._irep = rows.copy()
+
+    def set_mapping_info(self, rdb):
+        """rdb: the run's mapping_info (filter_reads.mapping_info).  genome_info() then carries the reference's reads_* columns and
+        filtered_read_pair_count (filter_reads.genome_wide_rr, a left merge on `genome`), after the coverage columns and before the
+        linkage columns, where genomeLevel_from_IS puts them (:213-228)"""
+        from . import filter_reads
+        self._rr = filter_reads.genome_wide_rr(rdb, self.stb)
 
     def irep_accessory(self):
         """one row per genome with the keys of the reference's accessory dict (irep_utilities.py:33-66)"""
@@ -334,14 +341,16 @@ class GenomeTables:
 
     def genome_info(self, skip_mm_profiling=False):
         """the reference's genome_info table (genomeLevel_from_IS): one row per genome and mm level, or per genome with
-        skip_mm_profiling (every scaffold's last level, no mm column); column names, order and dtypes as the reference's, without its
-        reads_* / filtered_read_pair_count columns (see the class)."""
+        skip_mm_profiling (every scaffold's last level, no mm column); column names, order and dtypes as the reference's; its
+        reads_* / filtered_read_pair_count columns only after set_mapping_info() (see the class)."""
         if self.mms is None:
             raise ValueError("GenomeTables.genome_info: no batch was added")
         skip = bool(skip_mm_profiling)
         gsi, relevant, cov_levels = self._scaffold_half(skip)
         eg, levels, mms = self._coverage_half(relevant, cov_levels, skip)
         mdb = pd.merge(gsi, eg, on=["genome", "mm"], how="outer")
+        if self._rr is not None:                                        # genomeUtilities.py:228: before the linkage columns
+            mdb = pd.merge(mdb, self._rr, on=["genome"], how="left")
         last = len(self.mms) - 1
         if int(self._ld["n"][:, last].sum()) > 0:                       # the run has linkage rows
             if int(self._ld["n"][:-1, last].sum()) > 0:                 # ... on scaffolds of the stb

@@ -23,7 +23,7 @@ import pandas as pd
 
 from .. import dist as idist
 from .. import _lib, engine
-from . import gene_profile, genome_utilities
+from . import filter_reads, gene_profile, genome_utilities
 from .snv_utilities import CLASSES, null_model_lut
 
 BASES = np.array(["A", "C", "T", "G", "N"])
@@ -745,6 +745,17 @@ def profile_options(kwargs):
     # what only a caller that shares the file's scan hands over (dist.profile_bam_sharded)
     o.scan_part, o.median_insert, o.filter_refs = kwargs.get('scan_part'), kwargs.get('median_insert'), kwargs.get('filter_refs')
     o.priority_reads = kwargs.get('priority_reads')
+    # the filters that read the read report (profile/fasta.py:87-136); --database_mode is three other flags (controller.py:210-214)
+    o.min_scaffold_reads = kwargs.get('min_scaffold_reads', 0) or 0
+    o.min_genome_coverage = kwargs.get('min_genome_coverage', 0) or 0
+    if kwargs.get('database_mode'):
+        o.filter['min_read_ani'] = 0.92
+        o.skip_mm = True
+        o.min_genome_coverage = 1
+    o.read_tables = kwargs.get('read_tables')
+    # (mapping_info, {removed scaffold: reason}) of the WHOLE file from a caller that shares the scan (dist.profile_bam_sharded): its handle
+    # has then run the final filter and dropped the removed scaffolds already -- neither happens again here
+    o.read_report_done = kwargs.get('read_report_done')
     return o
 
 
@@ -774,7 +785,8 @@ def select_scaffolds(refs, s2s, fasta_db, window_length, bam):
 
 
 def choose_read_pairs(bf, plan, n_refs, sR2M, opt):
-    """Which read pairs of the scanned file count, and with which mm: the controller's R2M, or the built-in filter"""
+    """Which read pairs of the scanned file count, and with which mm: the controller's R2M, or the built-in filter (-> the reference
+    indices that existed for it)"""
     if sR2M is None:
         if opt.priority_reads:
             bf.set_priority_reads(opt.priority_reads)
@@ -783,9 +795,10 @@ def choose_read_pairs(bf, plan, n_refs, sR2M, opt):
         wanted_tids = opt.filter_refs
         if wanted_tids is None:
             wanted_tids = [t for t, _, _ in plan] if len(plan) < n_refs else []
-        bf.set_wanted_refs(wanted_tids)
-        bf.filter(median_insert=opt.median_insert, **opt.filter)
-        return
+        if opt.read_report_done is None:            # (else the caller's handle is filtered, on the same set)
+            bf.set_wanted_refs(wanted_tids)
+            bf.filter(median_insert=opt.median_insert, **opt.filter)
+        return list(wanted_tids) if len(wanted_tids) else list(range(n_refs))
     for tid, name, _ in plan:
         r2m = sR2M.get(name, {})
         if isinstance(r2m, (set, frozenset, list, tuple)):       # --skip_mm_profiling: a set of pair names
@@ -793,6 +806,30 @@ def choose_read_pairs(bf, plan, n_refs, sR2M, opt):
         else:
             bf.set_r2m(tid, list(r2m.keys()), [0 if opt.skip_mm else int(v) for v in r2m.values()])
     bf.scan(part=opt.scan_part)                  # refresh the totals (max_mm now comes from the controller's values)
+
+
+def read_report_step(bf, plan, refs, wanted_tids, opt, stb):
+    """The read report of the filter that just ran and the scaffold filters that read it (controller.py:260-272): -> (mapping_info
+    over all wanted scaffolds, made before anything is dropped; {removed scaffold: reason}; the plan's rows that stay, still in
+    file order -- the reference sorts the survivors by read count, which no table depends on).  The handle forgets the removed
+    scaffolds' pairs (BamFile.drop_refs): the mm levels, the segment estimate and the batches then see only what will be profiled."""
+    names = [n for n, _, _ in refs]
+    if opt.read_report_done is not None:
+        rdb, removed = opt.read_report_done
+        return rdb, removed, [k for k, (_, name, _) in enumerate(plan) if name not in removed]
+    rdb = filter_reads.mapping_info(bf.read_report(), names, wanted_tids)
+    removed = {}
+    if opt.min_scaffold_reads or opt.min_genome_coverage:
+        s2p = rdb.set_index('scaffold')['filtered_pairs'].to_dict()
+        wanted = [names[t] for t in sorted(wanted_tids)]
+        _, removed = filter_reads.filter_scaffolds(wanted, s2p, {n: ln for n, ln, _ in refs}, float(rdb.loc[0, 'mean_pair_length']),
+                                                   min_scaffold_reads=opt.min_scaffold_reads, min_genome_coverage=opt.min_genome_coverage,
+                                                   stb=stb)
+        if removed:
+            tid_of = {n: t for t, n in enumerate(names)}
+            bf.drop_refs([tid_of[n] for n in removed])
+    keep = [k for k, (_, name, _) in enumerate(plan) if name not in removed]
+    return rdb, removed, keep
 
 
 def mm_levels(bf, skip_mm, strict):
@@ -1133,6 +1170,14 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     `pool_set` (a compare.SampleSet(pooling=True) whose pool_sites() has run) with `pool_sample` (default: the path): the second pass of
     SNV pooling -- every batch's slot is handed to SampleSet.pool_add before its release; a run with one mm bin then opens its pipe
     with want_counts (without `pool_set` nothing changes),
+    `read_tables` (dict that receives `mapping_info`, the reference's read report over all wanted scaffolds -- filter_reads.mapping_info,
+    made right after the read filter and before anything is dropped -- and `scaffolds_removed`, name -> reason; with `stb` and
+    `genome_tables` genome_info then carries the reads_* columns and filtered_read_pair_count), `min_scaffold_reads` /
+    `min_genome_coverage` (needs `stb`) / `database_mode` (= min_read_ani 0.92, skip_mm_profiling, min_genome_coverage 1,
+    controller.py:210-214): the scaffold filters that read the report (filter_reads.filter_scaffolds); a scaffold they drop leaves the plan
+    and the handle (BamFile.drop_refs) before the mm levels and the batches are made -- no SplitObject, no failure line; when nothing is
+    left the result is {} and one error line.  With `sR2M` no filter runs here: read_tables stays empty and the three keywords raise
+    ValueError (all of them off by default: a call without them does what it did),
     `batch_positions` / `batch_reads` (size of a device batch; `batch_observations` is accepted as 150 x batch_reads), `pipe_depth` (device batches in flight: the front end
     prepares batch k + 1 while batch k is profiled and its tables are cut), `stats` (dict that receives stage times).
     The BAM's reads go to the device as read segments (isx_pipe_submit_bam on a read-level pipe): the host never expands a
@@ -1148,6 +1193,13 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
     codes_of, layouts = [], []
     if kwargs.get('genes') is None and kwargs.get('gene_file'):        # a gene file the run cannot use is the caller's error, not a split's
         kwargs['genes'] = gene_profile.parse_genes(kwargs['gene_file'])
+    scaffold_filters = bool(opt.min_scaffold_reads or opt.min_genome_coverage)
+    if sR2M is not None and (scaffold_filters or kwargs.get('database_mode')):
+        raise ValueError("min_scaffold_reads / min_genome_coverage / database_mode read the report of the built-in read filter: "
+                         "with sR2M the controller has already filtered")
+    if opt.min_genome_coverage and kwargs.get('stb') is None:          # the reference asserts here (controller.py:216-218)
+        raise ValueError("If you adjust the minimum genome coverage, you need to provide an .stb!")
+    rdb = None
     try:
         ctx = kwargs.get('ctx') or engine.Context(opt.device)
         ctx.set_null_model(*null_model_lut(null_model))
@@ -1170,7 +1222,21 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
             bf.set_threads(opt.scan_threads)
         bf.scan(part=opt.scan_part)
         stage("scan_ms")
-        choose_read_pairs(bf, plan, len(refs), sR2M, opt)
+        wanted_tids = choose_read_pairs(bf, plan, len(refs), sR2M, opt)
+        if sR2M is None and (opt.read_tables is not None or scaffold_filters):
+            stb = genome_utilities.parse_stb(kwargs['stb']) if kwargs.get('stb') is not None else None
+            rdb, removed, keep = read_report_step(bf, plan, refs, wanted_tids, opt, stb)
+            if opt.read_tables is not None:
+                opt.read_tables['mapping_info'], opt.read_tables['scaffolds_removed'] = rdb, removed
+            if len(keep) < len(plan):               # the reference never schedules them: no SplitObject, no failure line
+                plan = [plan[k] for k in keep]
+                codes_of[:] = [codes_of[k] for k in keep]
+            if not plan:
+                line = "No scaffolds passed initial filtering based on numbers of mapped reads"      # controller.py:319-321
+                logging.error(line)
+                if logs is not None:
+                    logs.append(line)
+                return out
         n_mm, mm_values, mm_clamped = mm_levels(bf, opt.skip_mm, opt.strict)
         reads_per_ref, _ = bf.ref_counts()
         if not opt.store_everything:                # (--store_everything keys read_to_snvs by read name: the names stay)
@@ -1215,6 +1281,8 @@ def profile_bam(bam, fasta_db=None, sR2M=None, ISP_loc=None, **kwargs):
                 genomes.set_irep(irep.finish()[0])
                 if kwargs.get('irep_accessory'):
                     gt['iRep_accessory'] = genomes.irep_accessory()
+            if rdb is not None and opt.read_tables is not None:
+                genomes.set_mapping_info(rdb)
             gt['genome_info'] = genomes.genome_info(skip_mm_profiling=opt.skip_mm)
         if gset is not None:
             gene_profile.finish_genes(gset, kwargs['gene_tables'] if kwargs.get('gene_tables') is not None else {})

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the host BAM front end (isx_bam_open / isx_bam_expand): synthetic 2x150 bp pairs,
-written with a vectorised BAM writer.  usage: python tools/bench_front.py [n_pairs] [genome_len]"""
+written with a vectorised BAM writer; then the read filter (isx_bam_filter) and the read report after it
+(isx_bam_read_report), five handles each.  usage: python tools/bench_front.py [n_pairs] [genome_len] [n_refs]"""
 import os, struct, sys, time, zlib
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -58,9 +59,10 @@ def write_simple_bam(path, G, n_pairs, read_len=150, seed=1, n_refs=1):
 if __name__ == "__main__":
     n_pairs = int(float(sys.argv[1])) if len(sys.argv) > 1 else 200_000
     G = int(float(sys.argv[2])) if len(sys.argv) > 2 else 3_000_000
-    path = "/tmp/bench_front_%d.bam" % n_pairs
+    n_refs = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    path = "/tmp/bench_front_%d.bam" % n_pairs if n_refs == 1 else "/tmp/bench_front_%d_%d.bam" % (n_pairs, n_refs)
     if not os.path.exists(path):
-        t0 = time.time(); nb = write_simple_bam(path, G, n_pairs); print("wrote", path, nb, "bytes uncompressed in", round(time.time() - t0, 1), "s")
+        t0 = time.time(); nb = write_simple_bam(path, G, n_pairs, n_refs=n_refs); print("wrote", path, nb, "bytes uncompressed in", round(time.time() - t0, 1), "s")
     from instrain_amd import engine
     for rep in range(3):
         t0 = time.perf_counter()
@@ -74,3 +76,18 @@ if __name__ == "__main__":
         gbp = n_pairs * 300 / 1e9
         print("open %.3f s  expand %.3f s  -> %.3f Gbp/s  (%d obs, %.1f M reads/s)" %
               (t1 - t0, t2 - t1, gbp / (t2 - t0), n_obs, 2 * n_pairs / (t2 - t0) / 1e6), flush=True)
+    # the read filter and the read report that follows it (both host only), each on a fresh handle
+    for rep in range(5):
+        bf = engine.BamFile(path)
+        t0 = time.perf_counter()
+        bf.scan()
+        t1 = time.perf_counter()
+        bf.filter()
+        t2 = time.perf_counter()
+        line = "scan_ms %.1f  filter_ms %.2f" % (1e3 * (t1 - t0), 1e3 * (t2 - t1))
+        if hasattr(bf, "read_report"):
+            rows = bf.read_report()
+            t3 = time.perf_counter()
+            line += "  read_report_ms %.2f  (%d entries went through the pairing filter)" % (1e3 * (t3 - t2), int(rows["pass_pairing_filter"].sum()))
+        bf.close()
+        print(line, flush=True)
