@@ -310,7 +310,7 @@ def test_device_summary_big_and_small_scaffolds(skip_mm):
                 v = vals[~np.isnan(vals)]
                 assert d[cnt] == len(v), (i, m, cnt)
                 if len(v):
-                    assert d[med] == np.median(v.astype(np.float32)).astype(np.float64) or abs(d[med] - np.median(v)) < 1e-7, (i, m, med)
+                    assert d[med] == np.median(v), (i, m, med)        # float32 values in float64: their median is exact
                     assert abs(d[sm] - v.sum()) < 1e-6 * max(1.0, len(v))
 
 
