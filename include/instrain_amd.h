@@ -522,6 +522,17 @@ int isx_cmpset_add_profile(isx_cmpset *set, int32_t sample, int32_t n_scaffolds,
                            const int32_t *level_mm_values, const uint8_t *present, const int64_t *entry_offsets,
                            const uint32_t *positions, const uint32_t *values, int64_t n_snv, const isx_profile_snv *snv,
                            float *device_ms);
+/* The same for a set with pooling enabled (`inStrain compare -i ... --bams`: PoolController.__init__ reads the stored
+ * cumulative_snv_table, polymorpher.py:53-70).  Arguments, checks and what the call leaves as for isx_cmpset_add_profile -- the same
+ * code -- plus the sample's pool rows exactly as isx_cmpset_add leaves them: the highest-mm row of a position among the rows that are
+ * not cryptic (:65-68; a position whose rows are all cryptic is no own site), cnt = the stored row's A C T G.
+ *   snv_flags[n_snv]   bits 0..2 the row's class (the codes of isx_snv.cls), bit 3 cryptic; a class code above 5 or a bit above 3
+ *                      is ISX_ERR_ARG
+ * A set without pooling is ISX_ERR_STATE (isx_cmpset_add_profile is its call, which in turn keeps refusing a pooling set). */
+int isx_cmpset_add_profile_pool(isx_cmpset *set, int32_t sample, int32_t n_scaffolds, const int32_t *set_scaffold_ids, int32_t n_levels,
+                                const int32_t *level_mm_values, const uint8_t *present, const int64_t *entry_offsets,
+                                const uint32_t *positions, const uint32_t *values, int64_t n_snv, const isx_profile_snv *snv,
+                                const uint8_t *snv_flags, float *device_ms);
 
 /* sizes of the next isx_cmpset_compare (readComparer.py:162 over all samples): samples (highest index added + 1), axis levels, their real mm values (axis_mm[ISX_CMPSET_MAX_LEVELS] or NULL) */
 int isx_cmpset_axis(isx_cmpset *set, int32_t *n_samples, int32_t *n_levels, int32_t *axis_mm);
@@ -545,8 +556,9 @@ int isx_cmpset_fetch_snps(isx_cmpset *set, isx_compare_snp *rows);
  *   own row      the highest-mm row of a position among the rows that are NOT cryptic (:65-68)
  *   has          some level of the sample is present on the scaffold (the rule of isx_cmpset_compare)
  *   pooled       at least two samples have the scaffold (compare_controller.py:484); other scaffolds have no site
- * Order of calls: isx_cmpset_pool_enable, every isx_cmpset_add, isx_cmpset_pool_sites, isx_cmpset_pool_add for every batch again (the
- * "pull from the BAM"), isx_cmpset_pool_summary / isx_cmpset_pool_fetch_sample.  The samples share one reference (ref_base of a site is
+ * Order of calls: isx_cmpset_pool_enable, every isx_cmpset_add (or isx_cmpset_add_profile_pool), isx_cmpset_pool_sites,
+ * isx_cmpset_pool_add for every batch again (the "pull from the BAM"; or isx_cmpset_pool_add_obs ... isx_cmpset_pool_obs_done),
+ * isx_cmpset_pool_summary / isx_cmpset_pool_fetch_sample.  The samples share one reference (ref_base of a site is
  * taken from an own row).  A site without a sample at >= 5 reads, on which the reference raises (:524-529 inner join, then the int
  * cast), is reported with n_detect_5x = 0.  Integers only: two calls give identical bytes.
  * Device memory: 17 bytes x sites x samples + one bit per set position. */
@@ -577,8 +589,26 @@ int isx_cmpset_pool_fetch_sites(isx_cmpset *set, uint32_t *gpos);       /* [n_si
  * (sample, scaffold) twice, or a call before isx_cmpset_pool_sites: ISX_ERR_STATE. */
 int isx_cmpset_pool_add(isx_cmpset *set, int32_t sample, isx_batch *batch, int32_t n_batch_scaffolds, const int64_t *batch_scaffold_bounds,
                         const int32_t *set_scaffold_ids);
+/* The pull without a batch (extract_SNVS_from_bam, polymorpher.py:275-316, for a sample that came from a stored profile): pileup
+ * observations of the sample's reads go straight into its count columns.  Region i holds obs[obs_offsets[i] .. obs_offsets[i + 1]) of
+ * set scaffold set_scaffold_ids[i]; obs[k].gpos - gpos0[i] is the position on that scaffold (isx_bam_expand_region hands out positions
+ * on the reference: gpos0 = 0; after isx_bam_expand_refs it is the reference's flat start).  mm is ignored: every level counts
+ * (get_pooling_counts, :313-316); base 4 counts nowhere; an observation at a position that is no site, or a site the sample owns,
+ * changes nothing.  Counts are ADDED (integer atomics), so a scaffold may arrive in any number of calls and regions, column window
+ * after column window, in any order of observations -- but no column twice.  Regions of scaffolds with id -1, that the sample does not
+ * have or that are not pooled are skipped.  Checked on the host before anything is launched (ISX_ERR_ARG): obs_offsets start at 0,
+ * ascend and end at n_obs; ids inside the set; every position within its scaffold; base <= 4.  ISX_ERR_STATE: a call before
+ * isx_cmpset_pool_sites, a scaffold that is already pulled (by isx_cmpset_pool_add or isx_cmpset_pool_obs_done).  obs is host memory:
+ * one upload per call into scratch of the set.  *device_ms (may be NULL): the event-timed kernel. */
+int isx_cmpset_pool_add_obs(isx_cmpset *set, int32_t sample, int32_t n_regions, const int32_t *set_scaffold_ids, const int64_t *gpos0,
+                            const int64_t *obs_offsets, int64_t n_obs, const isx_obs *obs, float *device_ms);
+/* closes the (sample, scaffold)s: they are pulled, as after isx_cmpset_pool_add -- a scaffold that received no observation at all with
+ * zeros (the reference's "fill in blanks", polymorpher.py:306-308).  Ids -1, scaffolds the sample does not have or that are not
+ * pooled are skipped; a scaffold that is pulled already (twice in the list included) is ISX_ERR_STATE and nothing is closed.  A
+ * scaffold with observations under way is refused by isx_cmpset_pool_add (ISX_ERR_STATE). */
+int isx_cmpset_pool_obs_done(isx_cmpset *set, int32_t sample, int32_t n_scaffolds, const int32_t *set_scaffold_ids);
 /* PMdb (polymorpher.py:471-551): one row per site, cap_sites >= n_sites.  ISX_ERR_STATE (naming the first one) when a (sample,
- * scaffold) with sites still to pull was never handed to isx_cmpset_pool_add. */
+ * scaffold) with sites still to pull was never handed to isx_cmpset_pool_add / closed by isx_cmpset_pool_obs_done. */
 int isx_cmpset_pool_summary(isx_cmpset *set, int64_t cap_sites, isx_pool_site *out, float *device_ms);
 /* DSTdb columns of one sample (polymorpher.py:397-448): counts[n_sites][4] A C T G; meta[n_sites]: bit 0 the sample has the site's
  * scaffold (a row of DSTdb), bit 1 it owns the site, bits 2..4 the own row's class, bits 5..6 its con_base */

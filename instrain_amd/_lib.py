@@ -201,8 +201,8 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_batch_create", "isx_batch_create_reads", "isx_batch_destroy", "isx_batch_run", "isx_batch_launch", "isx_batch_wait", "isx_batch_sizes", "isx_batch_timings", "isx_batch_link_chain",
            "isx_batch_fetch_entries", "isx_batch_fetch_dense", "isx_batch_fetch_snv", "isx_batch_fetch_ld", "isx_batch_fetch_allele_obs",
            "isx_batch_summarize", "isx_batch_summarize_genomes", "isx_batch_genome_coverage", "isx_snv_level_counts", "isx_ld_level_sums", "isx_compare_coverage", "isx_compare_scaffolds", "isx_compare_fetch_snps",
-           "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_add_profile", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
-           "isx_cmpset_pool_enable", "isx_cmpset_pool_sites", "isx_cmpset_pool_fetch_sites", "isx_cmpset_pool_add", "isx_cmpset_pool_summary", "isx_cmpset_pool_fetch_sample",
+           "isx_cmpset_layout", "isx_cmpset_tiles", "isx_cmpset_level_map", "isx_cmpset_create", "isx_cmpset_destroy", "isx_cmpset_add", "isx_cmpset_add_profile", "isx_cmpset_add_profile_pool", "isx_cmpset_axis", "isx_cmpset_compare", "isx_cmpset_pair_snps", "isx_cmpset_fetch_snps",
+           "isx_cmpset_pool_enable", "isx_cmpset_pool_sites", "isx_cmpset_pool_fetch_sites", "isx_cmpset_pool_add", "isx_cmpset_pool_add_obs", "isx_cmpset_pool_obs_done", "isx_cmpset_pool_summary", "isx_cmpset_pool_fetch_sample",
            "isx_cluster_linkage", "isx_cmpset_cluster", "isx_cmpset_cluster_fetch_pairs", "isx_cmpset_cluster_fetch_linkage",
            "isx_irep_layout", "isx_irep_create", "isx_irep_destroy", "isx_irep_sizes", "isx_irep_add", "isx_irep_blocks_fetch", "isx_irep_blocks_add", "isx_irep_finish",
            "isx_genes_create", "isx_genes_destroy", "isx_genes_sites", "isx_batch_profile_genes", "isx_genes_profile_snvs",
@@ -287,6 +287,7 @@ def load():
     lib.isx_cmpset_destroy.restype = None
     lib.isx_cmpset_add.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     lib.isx_cmpset_add_profile.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp, C.POINTER(C.c_float)]
+    lib.isx_cmpset_add_profile_pool.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_axis.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp]
     lib.isx_cmpset_compare.argtypes = [vp, C.c_double, i64, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_pair_snps.argtypes = [vp, i32, i32, C.POINTER(i64)]
@@ -295,6 +296,8 @@ def load():
     lib.isx_cmpset_pool_sites.argtypes = [vp, C.POINTER(i64)]
     lib.isx_cmpset_pool_fetch_sites.argtypes = [vp, vp]
     lib.isx_cmpset_pool_add.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.isx_cmpset_pool_add_obs.argtypes = [vp, i32, i32, vp, vp, vp, i64, vp, C.POINTER(C.c_float)]
+    lib.isx_cmpset_pool_obs_done.argtypes = [vp, i32, i32, vp]
     lib.isx_cmpset_pool_summary.argtypes = [vp, i64, vp, C.POINTER(C.c_float)]
     lib.isx_cmpset_pool_fetch_sample.argtypes = [vp, i32, vp, vp]
     lib.isx_cluster_linkage.argtypes = [vp, i32, vp, vp, vp, i64, C.c_char_p, C.c_double, vp, vp, C.POINTER(C.c_float)]

@@ -167,8 +167,36 @@ def _series(ser, what, length):
     return pos.astype(np.uint32), val.astype(np.uint32)
 
 
-def pack_profile(index, lengths, covT, snv_table, mm_values=None):
-    """A stored profile as the arrays of isx_cmpset_add_profile; numpy only, no device.
+def _snv_flags(db):
+    """the snv_flags of isx_cmpset_add_profile_pool for the rows of a cumulative_snv_table: class code | cryptic << 3"""
+    from .profile.snv_utilities import CLASSES
+    for col in ("class", "cryptic"):
+        if col not in db.columns:
+            raise ValueError("pack_profile: pooling needs the SNV table's column %s" % col)
+    code = np.array([CLASSES.index(c) if c in CLASSES else -1 for c in db["class"].astype(object)], dtype=np.int64)
+    if (code < 0).any():
+        raise ValueError("pack_profile: the SNV table's column class holds %r"
+                         % sorted({str(c) for c, k in zip(db["class"].astype(object), code) if k < 0}))
+    cryptic = db["cryptic"].to_numpy()
+    if cryptic.dtype.kind not in "biuf" or not np.isin(cryptic, (0, 1)).all():
+        raise ValueError("pack_profile: the SNV table's column cryptic holds other values than True / False")
+    return (code | (cryptic.astype(np.int64) << 3)).astype(np.uint8)
+
+
+def pool_window(site_positions, owned):
+    """the columns [lo, hi) the reference piles up to pull one (sample, scaffold) (polymorpher.py:293: max(min(p) - 1, 0) to max(p) + 1
+    over the sites p the sample does not own) -> (lo, hi, n), None when there is nothing to pull.  site_positions: the scaffold's
+    sites as positions on the scaffold; owned: bool per site"""
+    p = np.asarray(site_positions, dtype=np.int64)[~np.asarray(owned, dtype=bool)]
+    if len(p) == 0:
+        return None
+    return max(int(p.min()) - 1, 0), int(p.max()) + 1, int(len(p))
+
+
+def pack_profile(index, lengths, covT, snv_table, mm_values=None, pool=False):
+    """A stored profile as the arrays of isx_cmpset_add_profile; numpy only, no device.  pool: also "flags" (uint8 per kept SNV row: the
+    snv_flags of isx_cmpset_add_profile_pool, from the table's `class` and `cryptic` columns -- a table without them, or with a class
+    name outside profile.snv_utilities.CLASSES, raises ValueError naming the column).
     index: scaffold name -> scaffold of the set; lengths: the set's lengths.  covT: {scaffold: {mm: pd.Series(values, index=positions)}}
     (emitters.load_special; (positions, values) tuples are taken too).  snv_table: the cumulative_snv_table (columns scaffold, position,
     mm, con_base, ref_base, var_base, allele_count, A, C, T, G; the old names conBase / refBase / varBase / baseCoverage are renamed as
@@ -210,6 +238,8 @@ def pack_profile(index, lengths, covT, snv_table, mm_values=None):
     out = {"scaffolds": names, "ids": np.array([i for i, _ in kept], dtype=np.int32), "levels": levels, "present": present,
            "offsets": offsets, "positions": np.concatenate(pos_parts), "values": np.concatenate(val_parts),
            "snv": np.zeros(0, dtype=_lib.PROFILE_SNV_DT)}
+    if pool:
+        out["flags"] = np.zeros(0, dtype=np.uint8)
     if snv_table is None or len(snv_table) == 0:
         return out
     db = snv_table.rename(columns=SNV_OLD_NAMES)
@@ -241,6 +271,8 @@ def pack_profile(index, lengths, covT, snv_table, mm_values=None):
         if pc.dtype.kind not in "iuf" or (pc != rows["cnt"].astype(np.int64).sum(axis=1)).any():
             raise ValueError("pack_profile: position_coverage is not A + C + T + G in every row")
     out["snv"] = rows
+    if pool:
+        out["flags"] = _snv_flags(db)
     return out
 
 
@@ -348,8 +380,20 @@ class SampleSet:
     def add_packed(self, sample_name, p, max_entries=1 << 26):
         """add_profile's second half: p = pack_profile(self.index, self.lengths, ...) of the sample, made earlier"""
         if self.pooling:                                        # (the library's own refusal, also for a profile with no scaffold of the set)
-            raise _lib.IsxError(-6, "add_profile: a set with pooling takes resident batches only (pooling needs the class / cryptic "
-                                    "columns of the sample's own rows, and reads to pull from)")
+            raise _lib.IsxError(-6, "add_profile: the own rows of a set with pooling need the class / cryptic columns of the SNV table: "
+                                    "add_profile_pooled takes them")
+        self._add_packed(sample_name, p, max_entries, False)
+
+    def add_profile_pooled(self, sample_name, covT, snv_table, mm_values=None, max_entries=1 << 26):
+        """add_profile for a set with pooling (`inStrain compare -i ... --bams`): the stored cumulative_snv_table -- with its `class` and
+        `cryptic` columns -- also gives the sample's own rows of pool_sites(), exactly as add_batch leaves them (PoolController.__init__,
+        polymorpher.py:53-70).  The pull then needs the sample's reads: pool_stored() / pool_add_obs() from its BAM, or pool_add() /
+        profile_bam(pool_set=...).  A set without pooling refuses (-6)."""
+        if not self.pooling:
+            raise _lib.IsxError(-6, "add_profile_pooled: the set keeps no pool rows (SampleSet(pooling=True)); add_profile is its call")
+        self._add_packed(sample_name, pack_profile(self.index, self.lengths, covT, snv_table, mm_values, pool=True), max_entries, True)
+
+    def _add_packed(self, sample_name, p, max_entries, pool):
         known = sample_name in self.samples
         sample = self.samples.index(sample_name) if known else len(self.samples)
         self.profile_device_ms = 0.0
@@ -368,12 +412,17 @@ class SampleSet:
             sub_off = np.ascontiguousarray(off[i0 * L:i1 * L + 1] - e0)
             positions, values = np.ascontiguousarray(p["positions"][e0:e1]), np.ascontiguousarray(p["values"][e0:e1])
             ids, present = np.ascontiguousarray(p["ids"][i0:i1]), np.ascontiguousarray(p["present"][i0:i1])
-            snv = p["snv"][(p["snv"]["scaffold"] >= i0) & (p["snv"]["scaffold"] < i1)].copy()
+            here = (p["snv"]["scaffold"] >= i0) & (p["snv"]["scaffold"] < i1)
+            snv = p["snv"][here].copy()
             snv["scaffold"] -= i0
             ms = C.c_float(0)
-            check(self.lib.isx_cmpset_add_profile(self.h, sample, i1 - i0, ids.ctypes.data, L, p["levels"].ctypes.data, present.ctypes.data,
-                                                  sub_off.ctypes.data, positions.ctypes.data, values.ctypes.data, len(snv),
-                                                  snv.ctypes.data, C.byref(ms)))
+            args = (self.h, sample, i1 - i0, ids.ctypes.data, L, p["levels"].ctypes.data, present.ctypes.data, sub_off.ctypes.data,
+                    positions.ctypes.data, values.ctypes.data, len(snv), snv.ctypes.data)
+            if pool:                                            # the flags follow their rows into the chunk
+                flags = np.ascontiguousarray(p["flags"][here])
+                check(self.lib.isx_cmpset_add_profile_pool(*args, flags.ctypes.data, C.byref(ms)))
+            else:
+                check(self.lib.isx_cmpset_add_profile(*args, C.byref(ms)))
             self.profile_device_ms += ms.value
             i0 = i1
         if not known:
@@ -462,6 +511,51 @@ class SampleSet:
             raise ValueError("pool_add: sample %r was never added" % (sample_name,))
         check(self.lib.isx_cmpset_pool_add(self.h, self.samples.index(sample_name), batch.h, len(ids), bb.ctypes.data, ids.ctypes.data))
 
+    # ---- the pull of a sample that came from a stored profile: observations of its BAM (isx_cmpset_pool_add_obs / _obs_done) ----
+    def pool_plan(self, sample_name):
+        """after pool_sites(): {scaffold name: (lo, hi, n_sites)} -- the columns [lo, hi) the reference would pile up for the sample
+        (pool_window) and the sites in them it has to pull; scaffolds with nothing to pull are left out"""
+        i = self.samples.index(sample_name)
+        n = self.n_pool_sites or 0
+        gpos = self.pool_site_positions().astype(np.int64)      # (no pool_sites() since the last add: the library refuses here)
+        counts, meta = np.zeros((n, 4), dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        check(self.lib.isx_cmpset_pool_fetch_sample(self.h, i, counts.ctypes.data, meta.ctypes.data))
+        scaf = np.searchsorted(self.offsets, gpos, side="right") - 1
+        plan = {}
+        for sc in np.unique(scaf[(meta & _lib.POOL_META_HAS) != 0]).tolist():
+            k = scaf == sc
+            w = pool_window(gpos[k] - self.offsets[sc], (meta[k] & _lib.POOL_META_OWN) != 0)
+            if w is not None:
+                plan[self.names[sc]] = w
+        return plan
+
+    def pool_add_obs(self, sample_name, scaffold_names, obs, obs_offsets, gpos0=None):
+        """pileup observations (engine.OBS_DT, host) of the sample's reads: region i = obs[obs_offsets[i]:obs_offsets[i + 1]] lies on
+        scaffold_names[i], at position obs["gpos"] - gpos0[i] (None: 0, what BamFile.expand_region hands out).  Every level counts, at
+        the sites the sample does not own; counts ADD, so a scaffold may come column window after column window -- but no column
+        twice -- and is closed by pool_obs_done().  -> the event-timed device ms of the call"""
+        if sample_name not in self.samples:
+            raise ValueError("pool_add_obs: sample %r was never added" % (sample_name,))
+        ids = np.array([self.index.get(n, -1) for n in scaffold_names], dtype=np.int32)
+        off = np.ascontiguousarray(obs_offsets, dtype=np.int64)
+        g0 = np.zeros(len(ids), dtype=np.int64) if gpos0 is None else np.ascontiguousarray(gpos0, dtype=np.int64)
+        if len(off) != len(ids) + 1 or len(g0) != len(ids):
+            raise ValueError("pool_add_obs: obs_offsets has one entry more than there are regions, gpos0 one per region")
+        obs = np.ascontiguousarray(obs, dtype=_lib.OBS_DT)
+        ms = C.c_float(0)
+        check(self.lib.isx_cmpset_pool_add_obs(self.h, self.samples.index(sample_name), len(ids), ids.ctypes.data, g0.ctypes.data,
+                                               off.ctypes.data, len(obs), obs.ctypes.data if len(obs) else None, C.byref(ms)))
+        return ms.value
+
+    def pool_obs_done(self, sample_name, scaffold_names=None):
+        """the sample's scaffolds (None: every scaffold of its pool_plan()) have brought all their observations: pulled, a scaffold
+        without any observation with zeros (polymorpher.py:306-308)"""
+        if sample_name not in self.samples:
+            raise ValueError("pool_obs_done: sample %r was never added" % (sample_name,))
+        names = list(self.pool_plan(sample_name)) if scaffold_names is None else list(scaffold_names)
+        ids = np.array([self.index.get(n, -1) for n in names], dtype=np.int32)
+        check(self.lib.isx_cmpset_pool_obs_done(self.h, self.samples.index(sample_name), len(ids), ids.ctypes.data if len(ids) else None))
+
     def pooled_tables(self):
         """-> (DSTdb, PMdb) of polymorpher.py:397-448 / :471-551 as pandas frames.  DSTdb: index (sample, position), columns A C T G and
         the categorical `scaffold`, rows by (scaffold in set order, sample in insertion order, position).  PMdb: index position, the
@@ -473,7 +567,15 @@ class SampleSet:
         n = self.n_pool_sites or 0                              # (None: the library refuses the call below)
         summary = np.zeros(n, dtype=_lib.POOL_SITE_DT)
         ms = C.c_float(0)
-        check(self.lib.isx_cmpset_pool_summary(self.h, n, summary.ctypes.data, C.byref(ms)))
+        try:
+            check(self.lib.isx_cmpset_pool_summary(self.h, n, summary.ctypes.data, C.byref(ms)))
+        except _lib.IsxError as e:                              # the library names the open (sample, scaffold) by index: add the names
+            import re
+            at = re.search(r"sample (\d+) has \d+ sites to pull on scaffold (\d+)", str(e))
+            if e.code != -6 or at is None:
+                raise
+            raise _lib.IsxError(-6, "%s (sample %r, scaffold %s)" % (str(e).split(": ", 1)[-1], self.samples[int(at.group(1))],
+                                                                     self.names[int(at.group(2))])) from None
         self.pool_device_ms = ms.value
         counts, meta = np.zeros((S, n, 4), dtype=np.uint32), np.zeros((S, n), dtype=np.uint8)
         for i in range(S):
@@ -567,6 +669,59 @@ class SampleSet:
             self.close()
         except Exception:
             pass
+
+
+def pool_stored(sset, name2bam, name2r2m=None, max_obs=1 << 24, **filter_flags):
+    """pull_SNVS_from_bams (polymorpher.py:102-130) for a pooling SampleSet whose samples came from stored profiles
+    (add_profile_pooled) and whose pool_sites() has run.  name2bam: sample -> its .bam.  Per sample: pool_plan(); the BAM is opened and
+    scanned once; per planned scaffold its read pairs are name2r2m[sample][scaffold] ({pair: mm} or pair names, through set_r2m) or,
+    where that is None / missing, the built-in filter with filter_flags (min_read_ani, min_mapq, max_insert_relative, min_insert,
+    pairing_filter) -- the convention of extract_SNVS_from_bam; then the planned columns [lo, hi) go through pool_add_obs() in column
+    windows and pool_obs_done() closes the sample.
+    The window rule: a scaffold starts with one window of all its hi - lo columns; a window that expands to more than max_obs
+    observations is dropped unsent and walked again at the width its own depth allows -- max_obs x columns / observations of the dropped
+    window, at most half its width, never below one column (which goes whatever it holds) -- and the rest of the scaffold keeps that
+    width.  So host and device staging stay near 8 bytes x max_obs at any depth, no column goes twice
+    and none is left out.
+    -> {sample: {"scaffolds", "windows", "observations", "device_ms"}}.  A planned scaffold the BAM does not name raises ValueError."""
+    from . import engine
+    fkw = dict(min_read_ani=filter_flags.get('min_read_ani', 0.95), min_mapq=filter_flags.get('min_mapq', -1),
+               max_insert_relative=filter_flags.get('max_insert_relative', 3), min_insert=filter_flags.get('min_insert', 50),
+               pairing_filter=filter_flags.get('pairing_filter', 'paired_only'))
+    out = {}
+    for name, bam in name2bam.items():
+        plan = sset.pool_plan(name)
+        stats = {"scaffolds": len(plan), "windows": 0, "observations": 0, "device_ms": 0.0}
+        bf = engine.BamFile(bam)
+        try:
+            tid = {n: i for i, (n, _, _) in enumerate(bf.refs())}
+            for scaffold in plan:
+                if scaffold not in tid:
+                    raise ValueError("scaffold {0} is not in the .bam file {1}!".format(scaffold, bam))
+            bf.scan()
+            r2m = {s: (name2r2m or {}).get(name, {}).get(s) for s in plan}
+            if any(m is None for m in r2m.values()):
+                bf.filter(**fkw)
+            for scaffold, m in r2m.items():
+                if m is not None:
+                    bf.set_r2m(tid[scaffold], list(m), None)
+            for scaffold, (lo, hi, _) in plan.items():
+                a, width = lo, hi - lo
+                while a < hi:
+                    b = min(a + width, hi)
+                    obs, _, _, _ = bf.expand_region(tid[scaffold], a, b, skip_mm=True, copy=False, **fkw)
+                    if len(obs) > max_obs and b - a > 1:           # the width the dropped window's depth allows, at most half
+                        width = max(1, min((b - a + 1) // 2, int(max_obs * (b - a) // len(obs))))
+                        continue
+                    stats["device_ms"] += sset.pool_add_obs(name, [scaffold], obs, [0, len(obs)])
+                    stats["windows"] += 1
+                    stats["observations"] += int(len(obs))
+                    a = b
+            sset.pool_obs_done(name, list(plan))
+        finally:
+            bf.close()
+        out[name] = stats
+    return out
 
 
 def genome_wide(table, stb, bin2length=None, mm_level=False):

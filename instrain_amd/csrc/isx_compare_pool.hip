@@ -9,7 +9,8 @@
 // Three passes over the set's word-aligned position space (isx_compare_set.hip):
 //   sites    every own row ORs its bit into the site plane; popcounts + one exclusive scan rank the sites, so the sites of a
 //            scaffold are a contiguous rank range; the own rows are scattered into counts[sample][rank] / meta[sample][rank]
-//   pull     a batch of the sample again: its count table read at the sites, or its entry table walked and added at the ranks
+//   pull     a batch of the sample again: its count table read at the sites, or its entry table walked and added at the ranks; or, for
+//            a sample that came from a stored profile, pileup observations of its BAM added at the ranks (k_pull_obs)
 //   summary  one thread per site over the samples
 // Integers only; the atomics are integer adds and ORs, so a call's bytes do not depend on timing.
 #include <algorithm>
@@ -146,6 +147,53 @@ __global__ void k_pull_entries(const isx_entry *entries, const uint32_t *win_nen
         uint32_t *c = reinterpret_cast<uint32_t *>(&counts[r]);
         for (int k = 0; k < 4; k++)
             if (e.cnt[k]) atomicAdd(&c[k], e.cnt[k]);
+    }
+}
+
+// pull, observation path (isx_cmpset_pool_add_obs): one lane per pileup observation, grid-stride.  The region of an observation is found
+// in the call's offsets (roff[lo] <= i < roff[lo + 1]; empty regions share an offset and the search lands behind them); rbase[region] is
+// the set position of the region's gpos 0, OBS_SKIP for a region the call leaves out.  Observations come column by column, so the
+// lanes of a wave mostly hit one (site, base) word: every run of equal (rank, base) keys in the wave -- found by comparing with the
+// lane below, the run heads collected by ballot -- makes ONE atomic add of the run's length.  Any order of observations is correct (a
+// run is whatever happens to be adjacent); -DISX_PULL_OBS_PLAIN builds the variant with one atomic per observation for the A/B.
+constexpr int64_t OBS_SKIP = INT64_MIN;
+constexpr int PULL_OBS_BLOCK = 256, PULL_OBS_MAX_BLOCKS = 2048;
+
+__global__ void __launch_bounds__(PULL_OBS_BLOCK) k_pull_obs(const isx_obs *obs, int64_t n_obs, const int64_t *roff, const int64_t *rbase,
+                                                             int n_regions, const uint64_t *plane, const uint32_t *word_rank, int64_t n_words,
+                                                             uint32_t n_sites, const uint8_t *meta, uint32_t *counts)
+{
+    constexpr unsigned long long NONE = ~0ull;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); i0 < n_obs; i0 += stride) {       // (wave-uniform)
+        const int64_t i = i0 + lane;
+        unsigned long long key = NONE;                  // rank * 4 + base of the word this observation counts in
+        if (i < n_obs) {
+            const isx_obs o = obs[i];
+            int lo = 0, hi = n_regions;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (roff[mid] <= i) lo = mid; else hi = mid;
+            }
+            const int64_t p0 = rbase[lo];
+            const int64_t sp = p0 + (int64_t)o.gpos;
+            if (o.base < 4 && p0 != OBS_SKIP && sp >= 0 && (sp >> 6) < n_words && (plane[sp >> 6] >> (sp & 63) & 1ull)) {
+                const uint32_t r = rank_of(plane, word_rank, (uint32_t)sp);
+                if (r < n_sites && !(meta[r] & META_OWN)) key = (unsigned long long)r * 4 + o.base;
+            }
+        }
+#ifdef ISX_PULL_OBS_PLAIN
+        if (key != NONE) atomicAdd(&counts[key], 1u);
+#else
+        const unsigned long long below = __shfl_up(key, 1);
+        const bool head = lane == 0 || below != key;
+        const unsigned long long heads = __ballot(head);
+        if (head && key != NONE) {
+            const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);          // the next head ends the run
+            atomicAdd(&counts[key], (uint32_t)(above ? __ffsll(above) : 64 - lane));
+        }
+#endif
     }
 }
 
@@ -361,7 +409,8 @@ int isx_cmpset_pool_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_
         }
         if (!st->p_has[(size_t)sample * n_scaf + sid] || !st->p_pooled[(size_t)sid]) continue;
         if (seen[(size_t)sid] || sm.pulled[(size_t)sid]) {
-            isx_set_error("isx_cmpset_pool_add: scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was pulled before");
+            isx_set_error("isx_cmpset_pool_add: scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) +
+                          (sm.pulled[(size_t)sid] == PULL_OBS ? " has observations of isx_cmpset_pool_add_obs under way" : " was pulled before"));
             return ISX_ERR_STATE;
         }
         seen[(size_t)sid] = 1;
@@ -403,7 +452,98 @@ int isx_cmpset_pool_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_
 #undef PA_TRY
         d_jobs.drop();
     }
-    for (int32_t sid : taken) sm.pulled[(size_t)sid] = 1;
+    for (int32_t sid : taken) sm.pulled[(size_t)sid] = PULL_DONE;
+    return ISX_OK;
+}
+
+int isx_cmpset_pool_add_obs(isx_cmpset *st, int32_t sample, int32_t n_regions, const int32_t *ids, const int64_t *gpos0, const int64_t *off,
+                            int64_t n_obs, const isx_obs *obs, float *device_ms)
+{
+    const std::string who("isx_cmpset_pool_add_obs: ");
+    if (device_ms) *device_ms = 0.f;
+    POOL_SITES(st, "isx_cmpset_pool_add_obs");
+    if (sample < 0 || n_regions < 0 || n_regions > (1 << 24) || n_obs < 0 || !off || (n_regions && (!ids || !gpos0)) || (n_obs && !obs)) {
+        isx_set_error(who + "bad argument");
+        return ISX_ERR_ARG;
+    }
+    if ((size_t)sample >= st->samples.size() || st->samples[(size_t)sample].mm.empty()) {
+        isx_set_error(who + "sample " + std::to_string(sample) + " was never added");
+        return ISX_ERR_ARG;
+    }
+    Sample &sm = st->samples[(size_t)sample];
+    const int32_t n_scaf = st->n_scaf;
+    if (off[0] != 0 || off[n_regions] != n_obs) { isx_set_error(who + "obs_offsets must start at 0 and end at n_obs"); return ISX_ERR_ARG; }
+    for (int i = 0; i < n_regions; i++)
+        if (off[i + 1] < off[i]) { isx_set_error(who + "obs_offsets must not descend"); return ISX_ERR_ARG; }
+    std::vector<int64_t> rbase((size_t)n_regions, OBS_SKIP);
+    std::vector<int32_t> taken;
+    for (int i = 0; i < n_regions; i++) {
+        const int32_t sid = ids[i];
+        if (sid < -1 || sid >= n_scaf) { isx_set_error(who + "set_scaffold_ids[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
+        const int64_t len = sid < 0 ? 0 : st->len[(size_t)sid];
+        for (int64_t k = off[i]; k < off[i + 1]; k++) {
+            const int64_t p = (int64_t)obs[k].gpos - gpos0[i];
+            if (obs[k].base > 4 || (sid >= 0 && (p < 0 || p >= len))) {
+                isx_set_error(who + "observation " + std::to_string(k) + " of region " + std::to_string(i) +
+                              (obs[k].base > 4 ? ": base code above 4" : ": position outside the scaffold"));
+                return ISX_ERR_ARG;
+            }
+        }
+        if (sid < 0 || !st->p_has[(size_t)sample * n_scaf + sid] || !st->p_pooled[(size_t)sid]) continue;
+        if (sm.pulled[(size_t)sid] == PULL_DONE) {
+            isx_set_error(who + "scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was pulled before");
+            return ISX_ERR_STATE;
+        }
+        rbase[(size_t)i] = st->spos[(size_t)sid] - gpos0[i];
+        taken.push_back(sid);
+    }
+    const uint32_t n = (uint32_t)st->n_sites;
+    if (n_obs && n && !taken.empty()) {
+        HIP_TRY(hipSetDevice(st->ctx->device));
+        hipStream_t s = st->ctx->stream;
+        const std::vector<int64_t> h_off(off, off + n_regions + 1);
+        HIP_TRY(st->obs_stage.fit((size_t)n_obs));
+        HIP_TRY(st->obs_roff.put(h_off, s)); HIP_TRY(st->obs_rbase.put(rbase, s));
+        HIP_TRY(hipMemcpyAsync(st->obs_stage.p, obs, (size_t)n_obs * sizeof(isx_obs), hipMemcpyHostToDevice, s));
+        const unsigned blocks = (unsigned)std::min<int64_t>((n_obs + PULL_OBS_BLOCK - 1) / PULL_OBS_BLOCK, PULL_OBS_MAX_BLOCKS);
+        HIP_TRY(hipEventRecord(st->ev[0], s));
+        hipLaunchKernelGGL(k_pull_obs, dim3(blocks), dim3(PULL_OBS_BLOCK), 0, s, st->obs_stage.p, n_obs, st->obs_roff.p, st->obs_rbase.p, n_regions,
+                           st->site_plane.p, st->word_rank.p, st->n_words, n, st->p_meta.p + (size_t)sample * n,
+                           reinterpret_cast<uint32_t *>(st->p_counts.p + (size_t)sample * n));
+        HIP_TRY(hipEventRecord(st->ev[1], s));
+        HIP_TRY(isx_wait_stream(s));
+        HIP_TRY(hipGetLastError());
+        if (device_ms) (void)hipEventElapsedTime(device_ms, st->ev[0], st->ev[1]);
+    }
+    for (int32_t sid : taken) sm.pulled[(size_t)sid] = PULL_OBS;
+    return ISX_OK;
+}
+
+int isx_cmpset_pool_obs_done(isx_cmpset *st, int32_t sample, int32_t n_ids, const int32_t *ids)
+{
+    const std::string who("isx_cmpset_pool_obs_done: ");
+    POOL_SITES(st, "isx_cmpset_pool_obs_done");
+    if (sample < 0 || n_ids < 0 || (n_ids && !ids)) { isx_set_error(who + "bad argument"); return ISX_ERR_ARG; }
+    if ((size_t)sample >= st->samples.size() || st->samples[(size_t)sample].mm.empty()) {
+        isx_set_error(who + "sample " + std::to_string(sample) + " was never added");
+        return ISX_ERR_ARG;
+    }
+    Sample &sm = st->samples[(size_t)sample];
+    const int32_t n_scaf = st->n_scaf;
+    std::vector<uint8_t> seen((size_t)n_scaf, 0);
+    std::vector<int32_t> taken;
+    for (int i = 0; i < n_ids; i++) {
+        const int32_t sid = ids[i];
+        if (sid < -1 || sid >= n_scaf) { isx_set_error(who + "set_scaffold_ids[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
+        if (sid < 0 || !st->p_has[(size_t)sample * n_scaf + sid] || !st->p_pooled[(size_t)sid]) continue;
+        if (seen[(size_t)sid] || sm.pulled[(size_t)sid] == PULL_DONE) {
+            isx_set_error(who + "scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was pulled before");
+            return ISX_ERR_STATE;
+        }
+        seen[(size_t)sid] = 1;
+        taken.push_back(sid);
+    }
+    for (int32_t sid : taken) sm.pulled[(size_t)sid] = PULL_DONE;      // (a scaffold without any observation: its counts are the zeros of pool_sites)
     return ISX_OK;
 }
 
@@ -415,9 +555,11 @@ int isx_cmpset_pool_summary(isx_cmpset *st, int64_t cap_sites, isx_pool_site *ou
     const int32_t S = (int32_t)st->samples.size();
     for (int32_t i = 0; i < S; i++)
         for (int32_t sc = 0; sc < st->n_scaf; sc++)
-            if (st->samples[(size_t)i].to_pull[(size_t)sc] > 0 && !st->samples[(size_t)i].pulled[(size_t)sc]) {
+            if (st->samples[(size_t)i].to_pull[(size_t)sc] > 0 && st->samples[(size_t)i].pulled[(size_t)sc] != PULL_DONE) {
                 isx_set_error("isx_cmpset_pool_summary: sample " + std::to_string(i) + " has " + std::to_string(st->samples[(size_t)i].to_pull[(size_t)sc]) +
-                              " sites to pull on scaffold " + std::to_string(sc) + " and was never handed to isx_cmpset_pool_add there");
+                              " sites to pull on scaffold " + std::to_string(sc) +
+                              (st->samples[(size_t)i].pulled[(size_t)sc] == PULL_OBS ? " and its observations were never closed by isx_cmpset_pool_obs_done"
+                                                                                     : " and was never handed to isx_cmpset_pool_add there"));
                 return ISX_ERR_STATE;
             }
     const uint32_t n = (uint32_t)st->n_sites;

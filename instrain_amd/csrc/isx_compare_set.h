@@ -21,6 +21,7 @@ struct PoolRow {                        // what pooling reads of an isx_snv: the
     uint32_t cnt[4];
 };
 static_assert(sizeof(PoolRow) == 24, "PoolRow is 24 bytes");
+enum : uint8_t { PULL_NONE = 0, PULL_DONE = 1, PULL_OBS = 2 };     // Sample::pulled
 
 struct PackJob {                        // one batch scaffold that the set names: its words as a run of the call's job words
     int64_t jw0;                        // first job word (ascending; a sentinel entry closes the list)
@@ -46,7 +47,8 @@ struct Sample {
     PoolRow *prows = nullptr;
     size_t n_prows = 0, cap_prows = 0;
     bool psorted = true;
-    std::vector<uint8_t> pulled;        // [n_scaf] isx_cmpset_pool_add has brought the scaffold since the last isx_cmpset_pool_sites
+    std::vector<uint8_t> pulled;        // [n_scaf] since the last isx_cmpset_pool_sites: PULL_DONE isx_cmpset_pool_add has brought the scaffold /
+                                        // isx_cmpset_pool_obs_done has closed it, PULL_OBS isx_cmpset_pool_add_obs has brought observations of it
     std::vector<int64_t> to_pull;       // [n_scaf] sites of the scaffold the sample does not own
 };
 
@@ -103,6 +105,7 @@ struct isx_cmpset {
     isxset::SetBuf<uint32_t> pf_pos, pf_val;
     isxset::SetBuf<isxset::ProfTile> pf_tiles;
     isxset::SetBuf<isx_profile_snv> pf_snv;
+    isxset::SetBuf<uint8_t> pf_flags;               // isx_cmpset_add_profile_pool: class / cryptic of every row of pf_snv
     // what the last isx_cmpset_compare left for isx_cmpset_pair_snps
     bool compared = false;
     double min_freq = 0.05;
@@ -133,6 +136,8 @@ struct isx_cmpset {
     isxset::SetBuf<int64_t> d_pwoff;                // [n_scaf + 1]
     isxset::SetBuf<uint32_t> d_srank, d_own;        // [n_scaf + 1]; [samples][n_scaf] own rows
     isxset::SetBuf<isx_pool_site> d_psum;
+    isxset::SetBuf<isx_obs> obs_stage;              // scratch of isx_cmpset_pool_add_obs: the call's observations, its regions' offsets
+    isxset::SetBuf<int64_t> obs_roff, obs_rbase;    // [n_regions + 1]; [n_regions] set position of the region's gpos 0 (OBS_SKIP: skipped)
     // strain clustering (isx_cluster.hip).  clustered: isx_cmpset_cluster has run since the last add / compare
     bool clustered = false;
     int64_t cl_P = 0;

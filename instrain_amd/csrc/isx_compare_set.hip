@@ -170,17 +170,34 @@ __global__ void k_pool_keys(const isx_snv *snv, uint32_t n, const int64_t *bboun
     idx[i] = i;
 }
 
+// the stored-record twin: a stored row has no class / cryptic fields, they come beside it (snv_flags: bits 0..2 class, bit 3 cryptic)
+__global__ void k_profile_pool_keys(const isx_profile_snv *snv, const uint8_t *snv_flags, uint32_t n, const int64_t *set_pos0, int n_cscaf,
+                                    uint64_t *keys, uint32_t *idx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t sc = snv[i].scaffold;
+    const int64_t p0 = sc >= 0 && sc < n_cscaf && !(snv_flags[i] & 8) ? set_pos0[sc] : -1;
+    keys[i] = p0 >= 0 ? ((uint64_t)(p0 + snv[i].position) << 16) | (uint32_t)(snv[i].mm & 0xFFFF) : ~0ull;
+    idx[i] = i;
+}
+
+__device__ __forceinline__ uint8_t class_of(const isx_snv &x, const uint8_t *, uint32_t) { return x.cls; }
+__device__ __forceinline__ uint8_t class_of(const isx_profile_snv &, const uint8_t *snv_flags, uint32_t i) { return snv_flags[i] & 7; }
+
+// Src: isx_snv (snv_flags unused) or isx_profile_snv with its snv_flags
+template <class Src>
 __global__ void k_gather_pool(const uint64_t *keys, const uint32_t *idx, const uint32_t *flags, const uint32_t *pos, uint32_t n,
-                              const isx_snv *snv, PoolRow *out, uint32_t cap, uint32_t *total)
+                              const Src *snv, const uint8_t *snv_flags, PoolRow *out, uint32_t cap, uint32_t *total)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (i + 1 == n) total[0] = pos[i] + flags[i];
     if (!flags[i] || pos[i] >= cap) return;
-    const isx_snv x = snv[idx[i]];
+    const Src x = snv[idx[i]];
     PoolRow r;
     r.gpos = (uint32_t)(keys[i] >> 16);
-    r.con_base = x.con_base; r.ref_base = x.ref_base; r.cls = x.cls; r.pad = 0;
+    r.con_base = x.con_base; r.ref_base = x.ref_base; r.cls = class_of(x, snv_flags, idx[i]); r.pad = 0;
     for (int k = 0; k < 4; k++) r.cnt[k] = x.cnt[k];
     out[pos[i]] = r;
 }
@@ -431,6 +448,39 @@ int launch_last_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv, const Src *d_sn
     return ISX_OK;
 }
 
+// The same tail for the pool rows (after reserve_last_rows, whose scratch it shares): room behind the sample's pool rows, then -- the
+// pooling keys in st->keys_in / idx_in -- sort, flag, scan, gather into PoolRow.
+int reserve_pool_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv)
+{
+    hipStream_t s = st->ctx->stream;
+    if (sm.cap_prows < sm.n_prows + n_snv) {
+        const size_t want = std::max(sm.n_prows + n_snv, sm.cap_prows * 2);
+        PoolRow *grown = nullptr;
+        HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(PoolRow)));
+        if (sm.n_prows) HIP_TRY(hipMemcpyAsync(grown, sm.prows, sm.n_prows * sizeof(PoolRow), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(isx_wait_stream(s));
+        if (sm.prows) isx_dev_free(sm.prows);
+        sm.prows = grown; sm.cap_prows = want;
+    }
+    return ISX_OK;
+}
+
+template <class Src>
+int launch_pool_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv, const Src *d_snv, const uint8_t *d_snv_flags, uint32_t *n_new)
+{
+    hipStream_t s = st->ctx->stream;
+    const dim3 blk(256), grid((n_snv + 255) / 256);
+    size_t tb = st->temp.cap;
+    HIP_TRY(rocprim::radix_sort_pairs(st->temp.p, tb, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
+    hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
+    tb = st->temp.cap;
+    HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_gather_pool<Src>, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, d_snv, d_snv_flags,
+                       sm.prows + sm.n_prows, (uint32_t)(sm.cap_prows - sm.n_prows), st->pos.p + n_snv);
+    HIP_TRY(hipMemcpyAsync(n_new, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
+    return ISX_OK;
+}
+
 // rows (compare rows or pool rows) of a sample whose batches did not arrive in set order: one sort by position
 template <class Row>
 int sort_rows_of(isx_cmpset *st, Row *&rows, size_t n_rows, size_t cap_rows, bool &sorted)
@@ -536,6 +586,8 @@ void isx_cmpset_destroy(isx_cmpset *st)
     st->bbounds.drop(); st->set_pos0.drop(); st->acc.drop(); st->temp.drop(); st->jobs.drop(); st->keys.drop(); st->keys_in.drop();
     st->d_planes.drop(); st->d_rows.drop(); st->d_n_rows.drop(); st->d_failed.drop(); st->d_cursor.drop(); st->d_lmap.drop();
     st->d_pres.drop(); st->d_spos.drop(); st->d_axis.drop(); st->d_cnt.drop(); st->d_snp.drop(); st->snp_rows.drop();
+    st->pf_off.drop(); st->pf_pos.drop(); st->pf_val.drop(); st->pf_tiles.drop(); st->pf_snv.drop(); st->pf_flags.drop();
+    st->obs_stage.drop(); st->obs_roff.drop(); st->obs_rbase.drop();
     for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
     delete st;
 }
@@ -617,14 +669,9 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     if (n_snv) {
         const int rc = reserve_last_rows(st, sm, n_snv);
         if (rc) return rc;
-        if (st->pool_on && sm.cap_prows < sm.n_prows + n_snv) {
-            const size_t want = std::max(sm.n_prows + n_snv, sm.cap_prows * 2);
-            PoolRow *grown = nullptr;
-            HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(PoolRow)));
-            if (sm.n_prows) HIP_TRY(hipMemcpyAsync(grown, sm.prows, sm.n_prows * sizeof(PoolRow), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(isx_wait_stream(s));
-            if (sm.prows) isx_dev_free(sm.prows);
-            sm.prows = grown; sm.cap_prows = want;
+        if (st->pool_on) {
+            const int rcp = reserve_pool_rows(st, sm, n_snv);
+            if (rcp) return rcp;
         }
     }
     SummaryIn in{};
@@ -654,14 +701,8 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     if (n_snv && st->pool_on) {
         const dim3 grid((n_snv + 255) / 256);
         hipLaunchKernelGGL(k_pool_keys, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
-        size_t tb = st->temp.cap;
-        HIP_TRY(rocprim::radix_sort_pairs(st->temp.p, tb, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
-        hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
-        tb = st->temp.cap;
-        HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
-        hipLaunchKernelGGL(k_gather_pool, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, b->d_snv,
-                           sm.prows + sm.n_prows, (uint32_t)(sm.cap_prows - sm.n_prows), st->pos.p + n_snv);
-        HIP_TRY(hipMemcpyAsync(&n_new_pool, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
+        const int rc = launch_pool_rows(st, sm, n_snv, b->d_snv, (const uint8_t *)nullptr, &n_new_pool);
+        if (rc) return rc;
     }
     HIP_TRY(isx_wait_stream(s));
     HIP_TRY(hipGetLastError());
@@ -680,19 +721,24 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     return ISX_OK;
 }
 
-int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, const int32_t *ids, int32_t L, const int32_t *level_mm_values,
-                           const uint8_t *present, const int64_t *off, const uint32_t *positions, const uint32_t *values, int64_t n_snv_in,
-                           const isx_profile_snv *snv, float *device_ms)
+// both stored-profile entry points.  pool: isx_cmpset_add_profile_pool, snv_flags beside the rows; otherwise isx_cmpset_add_profile
+static int add_profile(bool pool, isx_cmpset *st, int32_t sample, int32_t n_cscaf, const int32_t *ids, int32_t L, const int32_t *level_mm_values,
+                       const uint8_t *present, const int64_t *off, const uint32_t *positions, const uint32_t *values, int64_t n_snv_in,
+                       const isx_profile_snv *snv, const uint8_t *snv_flags, float *device_ms)
 {
-    const std::string who("isx_cmpset_add_profile: ");
+    const std::string who(pool ? "isx_cmpset_add_profile_pool: " : "isx_cmpset_add_profile: ");
     if (device_ms) *device_ms = 0.f;
     if (!st || sample < 0 || sample >= ISX_CMPSET_MAX_SAMPLES || n_cscaf <= 0 || !ids || L <= 0 || !level_mm_values || !present || !off ||
-        n_snv_in < 0 || (n_snv_in && !snv)) {
+        n_snv_in < 0 || (n_snv_in && (!snv || (pool && !snv_flags)))) {
         isx_set_error(who + "bad argument");
         return ISX_ERR_ARG;
     }
-    if (st->pool_on) {
-        isx_set_error(who + "a set with pooling enabled takes resident batches only (its own rows need the class / cryptic columns, the pull needs reads)");
+    if (st->pool_on && !pool) {
+        isx_set_error(who + "the own rows of a set with pooling enabled need the class / cryptic columns: isx_cmpset_add_profile_pool takes them");
+        return ISX_ERR_STATE;
+    }
+    if (pool && !st->pool_on) {
+        isx_set_error(who + "the set keeps no pool rows (isx_cmpset_pool_enable before the first add); isx_cmpset_add_profile is its call");
         return ISX_ERR_STATE;
     }
     if (L > ISX_CMPSET_MAX_LEVELS) {
@@ -763,6 +809,10 @@ int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, cons
             isx_set_error(who + "SNV row " + std::to_string(r) + ": scaffold index, position, mm or a base code out of range");
             return ISX_ERR_ARG;
         }
+        if (pool && ((snv_flags[r] & 7) > 5 || (snv_flags[r] & ~15))) {
+            isx_set_error(who + "snv_flags[" + std::to_string(r) + "]: a class code above 5 or a bit above 3");
+            return ISX_ERR_ARG;
+        }
     }
     if (sub_scaf.empty()) return ISX_OK;            // nothing of this call is in the set
     // the tiles: the set's tile geometry over the call's scaffolds only
@@ -799,8 +849,10 @@ int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, cons
     // scratch and uploads, all sized before anything is launched
     HIP_TRY(st->pf_off.fit((size_t)n_series + 1)); HIP_TRY(st->pf_pos.fit((size_t)n_entries)); HIP_TRY(st->pf_val.fit((size_t)n_entries));
     HIP_TRY(st->pf_snv.fit(n_snv));
+    if (pool) HIP_TRY(st->pf_flags.fit(n_snv));
     if (n_snv) {
-        const int rc = reserve_last_rows(st, sm, n_snv);
+        int rc = reserve_last_rows(st, sm, n_snv);
+        if (!rc && pool) rc = reserve_pool_rows(st, sm, n_snv);
         if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(st->pf_off.p, off, ((size_t)n_series + 1) * 8, hipMemcpyHostToDevice, s));
@@ -809,6 +861,7 @@ int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, cons
         HIP_TRY(hipMemcpyAsync(st->pf_val.p, values, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
     }
     if (n_snv) HIP_TRY(hipMemcpyAsync(st->pf_snv.p, snv, (size_t)n_snv * sizeof(isx_profile_snv), hipMemcpyHostToDevice, s));
+    if (n_snv && pool) HIP_TRY(hipMemcpyAsync(st->pf_flags.p, snv_flags, n_snv, hipMemcpyHostToDevice, s));
     HIP_TRY(st->pf_tiles.put(tiles, s));
     HIP_TRY(st->set_pos0.put(set_pos0, s));
     HIP_TRY(hipEventRecord(st->ev[0], s));
@@ -819,6 +872,13 @@ int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, cons
         hipLaunchKernelGGL(k_profile_keys, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, n_snv, st->set_pos0.p, (int)n_cscaf,
                            st->keys_in.p, st->idx_in.p);
         const int rc = launch_last_rows(st, sm, n_snv, st->pf_snv.p, &n_new);
+        if (rc) return rc;
+    }
+    uint32_t n_new_pool = 0;                        // pool rows: as isx_cmpset_add makes them, the cryptic rows keyed out
+    if (n_snv && pool) {
+        hipLaunchKernelGGL(k_profile_pool_keys, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, st->pf_flags.p, n_snv, st->set_pos0.p,
+                           (int)n_cscaf, st->keys_in.p, st->idx_in.p);
+        const int rc = launch_pool_rows(st, sm, n_snv, st->pf_snv.p, st->pf_flags.p, &n_new_pool);
         if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(st->ev[1], s));
@@ -834,8 +894,24 @@ int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, cons
     }
     if (n_new && sm.n_rows && min_sid < sm.max_sid) sm.sorted = false;
     sm.n_rows += std::min<size_t>(n_new, sm.cap_rows - sm.n_rows);
+    if (n_new_pool && sm.n_prows && min_sid < sm.max_sid) sm.psorted = false;
+    sm.n_prows += std::min<size_t>(n_new_pool, sm.cap_prows - sm.n_prows);
     sm.max_sid = std::max(sm.max_sid, max_sid);
     return ISX_OK;
+}
+
+int isx_cmpset_add_profile(isx_cmpset *st, int32_t sample, int32_t n_cscaf, const int32_t *ids, int32_t L, const int32_t *level_mm_values,
+                           const uint8_t *present, const int64_t *off, const uint32_t *positions, const uint32_t *values, int64_t n_snv,
+                           const isx_profile_snv *snv, float *device_ms)
+{
+    return add_profile(false, st, sample, n_cscaf, ids, L, level_mm_values, present, off, positions, values, n_snv, snv, nullptr, device_ms);
+}
+
+int isx_cmpset_add_profile_pool(isx_cmpset *st, int32_t sample, int32_t n_cscaf, const int32_t *ids, int32_t L, const int32_t *level_mm_values,
+                                const uint8_t *present, const int64_t *off, const uint32_t *positions, const uint32_t *values, int64_t n_snv,
+                                const isx_profile_snv *snv, const uint8_t *snv_flags, float *device_ms)
+{
+    return add_profile(true, st, sample, n_cscaf, ids, L, level_mm_values, present, off, positions, values, n_snv, snv, snv_flags, device_ms);
 }
 
 int isx_cmpset_axis(isx_cmpset *st, int32_t *n_samples, int32_t *n_levels, int32_t *axis_mm)
