@@ -722,6 +722,46 @@ int isx_genes_profile_snvs(isx_genes *g, int32_t n_scaffolds, const int64_t *sca
                            const int32_t *gene_last, int64_t n_snv, const isx_snv *snv, int32_t n_levels, isx_gene_mutation *mut_out,
                            isx_gene_snv_count *cnt_out, float *device_ms);
 
+/* ---- gene and genome tables from a STORED profile (`inStrain profile_genes -i IS`: GeneProfile.py:304-422 on covT / clonT of
+ *      raw_data; `inStrain genome_wide -i IS`: genomeUtilities.py:145-269 genomeLevel_from_IS) ----
+ * A stored profile keeps covT / clonT / clonTR as one sparse series (position -> value) per (scaffold, mm key).  isx_stored holds
+ * the series of some scaffolds on the device, laid out over one flat space (scaffold_bounds, as for isx_batch_summarize) and
+ * LEVEL-MAJOR: level k of the object is the k-th of the profile's mm values (the caller keeps the values), and per table the entries of
+ * level k are [offsets[k], offsets[k + 1]) of gpos / values, ordered by flat position -- scaffold after scaffold, ascending inside one.
+ * The passes below materialise the levels as the isx_batch_* calls of the same name do (coverage adds up over the levels, a clonality
+ * replaces that of a lower level) and then run the same kernels, so their outputs have the same shapes and meaning; level k of an
+ * output is level k of the object.
+ *   cov_present / clon_present [n_scaffolds][n_levels]   the level's mm is a key of covT / clonT of the scaffold (an empty series under a
+ *                              key is legal; a series under no key is refused).  clon_present may be NULL without clonT; it is the
+ *                              caller's to mask clonality rows with -- the device reads cov_present (isx_scaffold_level.present,
+ *                              ISX_GENE_LEVEL_PRESENT).  clonTR entries are not held against either.
+ *   clon_offsets / clonr_offsets NULL   the profile has no clonT / clonTR: nothing is applied to that array
+ *   ref_codes                  NULL, or the base code (0..4) of every flat position: what isx_irep_add_stored counts G+C from
+ * Everything is checked on the host before anything is uploaded or launched, and a refused call leaves nothing behind: bounds as for
+ * isx_batch_genome_coverage with the flat space below 2^32 positions; 1 <= n_levels <= 128 (more: ISX_ERR_CAPACITY); offsets start at
+ * 0 and ascend; inside a level gpos ascends strictly and stays below scaffold_bounds[n_scaffolds]; clonalities are finite and in (0, 1].
+ * Every other violation is ISX_ERR_ARG with the argument's name in the message.  The object owns its device copies, its scratch
+ * arrays, a stream and two events; the host arrays may be freed after the call. */
+typedef struct isx_stored isx_stored;
+int  isx_stored_create(isx_ctx *ctx, int32_t n_scaffolds, const int64_t *scaffold_bounds, int32_t n_levels,
+                       const uint8_t *cov_present, const uint8_t *clon_present,
+                       const int64_t *cov_offsets,   const uint32_t *cov_gpos,   const uint32_t *cov_values,
+                       const int64_t *clon_offsets,  const uint32_t *clon_gpos,  const float *clon_values,
+                       const int64_t *clonr_offsets, const uint32_t *clonr_gpos, const float *clonr_values,
+                       const uint8_t *ref_codes,
+                       isx_stored **out);
+void isx_stored_destroy(isx_stored *stored);
+/* out[n_scaffolds][n_levels] as isx_batch_summarize */
+int  isx_stored_summarize(isx_stored *stored, isx_scaffold_level *out, float *device_ms);
+/* acc[n_genomes][n_levels], hist[n_genomes][n_levels][hist_bins] as isx_batch_genome_coverage */
+int  isx_stored_genome_coverage(isx_stored *stored, const int32_t *scaffold_genome, int32_t n_genomes, int32_t mask_edges,
+                                int32_t hist_bins, isx_genome_cov *acc, uint32_t *hist, float *device_ms);
+/* cov_out[n_call_genes][n_levels], scaffold_flags[n_scaffolds][n_levels] as isx_batch_profile_genes */
+int  isx_stored_profile_genes(isx_stored *stored, isx_genes *genes, const int32_t *gene_first, const int32_t *gene_last,
+                              isx_gene_cov *cov_out, uint8_t *scaffold_flags, float *device_ms);
+/* isx_irep_add for a stored profile: set_index[n_scaffolds of the object], level as there.  Without ref_codes: ISX_ERR_STATE. */
+int  isx_irep_add_stored(isx_irep *irep, isx_stored *stored, const int32_t *set_index, int32_t level, float *device_ms);
+
 /* ---- streaming hand-over: profile a stream of batches, each exactly once ----
  * What production does (the reference's analogue is the command / result queue pair around its worker pool,
  * profile_controller.py:157-193, 243-271): batches arrive from the host, are profiled once and their tables go

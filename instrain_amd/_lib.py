@@ -206,6 +206,7 @@ SYMBOLS = ["isx_last_error", "isx_abi_version", "isx_ctx_create", "isx_ctx_destr
            "isx_cluster_linkage", "isx_cmpset_cluster", "isx_cmpset_cluster_fetch_pairs", "isx_cmpset_cluster_fetch_linkage",
            "isx_irep_layout", "isx_irep_create", "isx_irep_destroy", "isx_irep_sizes", "isx_irep_add", "isx_irep_blocks_fetch", "isx_irep_blocks_add", "isx_irep_finish",
            "isx_genes_create", "isx_genes_destroy", "isx_genes_sites", "isx_batch_profile_genes", "isx_genes_profile_snvs",
+           "isx_stored_create", "isx_stored_destroy", "isx_stored_summarize", "isx_stored_genome_coverage", "isx_stored_profile_genes", "isx_irep_add_stored",
            "isx_pipe_create", "isx_pipe_destroy", "isx_pipe_submit", "isx_pipe_submit_reads", "isx_pipe_stage_reads", "isx_pipe_submit_wire", "isx_wire_bytes", "isx_wire_free", "isx_wire_keep_reference", "isx_pipe_submit_bam", "isx_encode_segs", "isx_encode_segs_ring", "isx_seg_records_needed", "isx_encode_delta", "isx_delta_records_needed", "isx_count_read_segs", "isx_pack_reads", "isx_pipe_collect", "isx_pipe_release", "isx_pipe_fetch_entries", "isx_pipe_fetch_entries_shrunk", "isx_levels_expand", "isx_encode_obs", "isx_encode_obs_ring",
            "isx_pack_ref_planes", "isx_planes_from_segs", "isx_pack_read_planes", "isx_pipe_submit_planes", "isx_pipe_stage_planes", "isx_encode_planes", "isx_encode_planes_mm", "isx_pipe_set_reference_budget", "isx_host_register", "isx_host_unregister",
            "isx_bgzf_index", "isx_bgzf_inflate_device", "isx_bgzf_inflate_host", "isx_bgzf_inflate_fast",
@@ -319,6 +320,13 @@ def load():
     lib.isx_genes_sites.argtypes = [vp, vp, C.POINTER(C.c_float)]
     lib.isx_batch_profile_genes.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
     lib.isx_genes_profile_snvs.argtypes = [vp, i32, vp, vp, vp, i64, vp, i32, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_stored_create.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.isx_stored_destroy.argtypes = [vp]
+    lib.isx_stored_destroy.restype = None
+    lib.isx_stored_summarize.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    lib.isx_stored_genome_coverage.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_stored_profile_genes.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+    lib.isx_irep_add_stored.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_float)]
     lib.isx_pipe_create.argtypes = [vp, C.POINTER(Params), C.POINTER(PipeParams), C.POINTER(vp)]
     lib.isx_pipe_destroy.argtypes = [vp]
     lib.isx_pipe_destroy.restype = None

@@ -430,6 +430,49 @@ int isx_irep_add(isx_irep *st, isx_batch *b, int32_t n_bscaf, const int64_t *bb,
     return ISX_OK;
 }
 
+int isx_irep_add_stored(isx_irep *st, isx_stored *sp, const int32_t *set_index, int32_t level, float *device_ms)
+{
+    if (!st || !sp || !set_index) { isx_set_error("isx_irep_add_stored: bad argument"); return ISX_ERR_ARG; }
+    if (sp->ctx != st->ctx) { isx_set_error("isx_irep_add_stored: the stored profile belongs to another ctx than the accumulator"); return ISX_ERR_ARG; }
+    if (level < -1 || level >= sp->M) {
+        isx_set_error("isx_irep_add_stored: level " + std::to_string(level) + " outside [-1, " + std::to_string(sp->M) + ")");
+        return ISX_ERR_ARG;
+    }
+    const int32_t n_bscaf = sp->n_scaf;
+    const int64_t *bb = sp->bounds.data();
+    std::vector<int64_t> base((size_t)n_bscaf, -1);
+    std::vector<uint8_t> mine((size_t)st->n_scaf, 0);
+    for (int32_t i = 0; i < n_bscaf; i++) {
+        const int32_t sid = set_index[i];
+        if (sid == -1) continue;
+        if (sid < 0 || sid >= st->n_scaf) { isx_set_error("isx_irep_add_stored: set_index[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
+        if (bb[i + 1] - bb[i] != st->len[(size_t)sid]) {
+            isx_set_error("isx_irep_add_stored: scaffold " + std::to_string(i) + " has not the length of set scaffold " + std::to_string(sid));
+            return ISX_ERR_ARG;
+        }
+        if (st->seen[(size_t)sid] || mine[(size_t)sid]) {
+            isx_set_error("isx_irep_add_stored: scaffold " + std::to_string(sid) + " was added before");
+            return ISX_ERR_STATE;
+        }
+        mine[(size_t)sid] = 1;
+        base[(size_t)i] = st->base[(size_t)sid];
+    }
+    if (!sp->d_ref) { isx_set_error("isx_irep_add_stored: the stored profile was created without ref_codes"); return ISX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    SummaryIn in{};
+    stored_summary_in(sp, in);
+    IrepAdd a{};
+    a.scaffold_base = base.data(); a.level = level; a.mask_edges = st->mask;
+    a.ref = sp->d_ref; a.ref_n = nullptr; a.ref_packed = 0;
+    a.block_cov = st->d_cov; a.block_gc = st->d_gc;
+    const int rc = run_irep_add(in, sp->S, a, device_ms);
+    if (rc) return rc;
+    for (int32_t i = 0; i < st->n_scaf; i++) st->seen[(size_t)i] |= mine[(size_t)i];
+    HIP_TRY(hipMemcpyAsync(st->d_seen, st->seen.data(), (size_t)st->n_scaf, hipMemcpyHostToDevice, st->ctx->stream));
+    HIP_TRY(isx_wait_stream(st->ctx->stream));
+    return ISX_OK;
+}
+
 int isx_irep_blocks_fetch(isx_irep *st, uint64_t *cov, uint32_t *gc, uint8_t *seen)
 {
     if (!st || !cov || !gc || !seen) { isx_set_error("isx_irep_blocks_fetch: bad argument"); return ISX_ERR_ARG; }

@@ -23,6 +23,15 @@ struct SummaryBuffers {
     void fit_positions(size_t n_pos);
 };
 
+// sparse source (isx_stored.hip): a stored profile's covT / clonT / clonTR as level-major CSRs on the device, one (flat position,
+// value) pair per entry -- coverage as uint32, clonalities as float bits -- so that a lane loads an entry with one 8-byte read.
+// Table t (0 covT, 1 clonT, 2 clonTR) has the entries [off[t][mm], off[t][mm + 1]) at level mm, ordered by flat position.
+struct SparseLevels {
+    const uint2 *pairs[3];          // device; NULL: the profile has no such table
+    const int64_t *off[3];          // host, [M + 1]
+    const uint8_t *cov_present;     // device, [n_scaffolds][M]: the level is a key of the scaffold's covT
+};
+
 struct SummaryIn {
     hipStream_t stream;
     hipEvent_t *ev;                 // 2 events
@@ -40,6 +49,8 @@ struct SummaryIn {
     const uint32_t *win_nent;
     uint32_t slab, n_win, n_ovf;
     uint64_t ovf0;
+    // sparse path (not NULL: the source, whatever M is)
+    const SparseLevels *sparse;
 };
 
 // (position, value) pairs ordered by position: a 32-bit radix sort of the 8-byte entries on their low word; *temp grows on demand
@@ -153,5 +164,22 @@ struct IrepAdd {
 void launch_irep_blocks(hipStream_t s, const uint32_t *cov, uint32_t n_pos, const int64_t *sbounds, const int64_t *sbase, int n_scaf,
                         int mask_edges, const uint8_t *ref, int ref_packed, const uint8_t *ref_n, uint64_t *block_cov, uint32_t *block_gc);
 int run_irep_add(const SummaryIn &in, SummaryBuffers &B, const IrepAdd &a, float *ms);
+// ---- a stored profile's level series resident on the device (isx_stored.hip): the third source of the passes above ----
+struct isx_stored {
+    isx_ctx *ctx = nullptr;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int32_t n_scaf = 0, M = 0;
+    std::vector<int64_t> bounds;        // [n_scaf + 1]
+    std::vector<int64_t> off[3];        // covT, clonT, clonTR: [M + 1], empty = no such table
+    uint2 *d_pairs[3] = {nullptr, nullptr, nullptr};
+    uint8_t *d_present = nullptr;       // cov_present
+    uint8_t *d_ref = nullptr;           // base codes 0..4 per flat position, or NULL
+    SparseLevels view{};
+    SummaryBuffers S;
+};
+void stored_summary_in(isx_stored *st, SummaryIn &in);
+
 int run_ld_levels(int device, hipStream_t s, int32_t n_scaffolds, const int64_t *scaffold_bounds, int64_t n_ld, const isx_ld *ld,
                   int32_t n_levels, isx_ld_level *out, float *device_ms);

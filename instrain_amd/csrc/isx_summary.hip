@@ -92,6 +92,62 @@ __global__ void k_level_apply(const isx_entry *entries, const uint32_t *win_nent
     }
 }
 
+// sparse path: add level `mm` of a stored profile (three level-major CSRs, isx_stored.hip) onto the running arrays.  The three
+// slices of the level -- coverage, clonality, rarefied clonality -- are consecutive index ranges of one grid-stride loop; lanes take
+// consecutive entries, one 8-byte (position, value) load each, and positions ascend within a slice, so the writes of a dense series
+// land next to each other.  A flat position occurs at most once per level and table (checked on the host before the upload), so
+// plain read-modify-writes are race free, as in k_level_apply.  Acc.present is the uploaded covT-key flag: nothing here looks a
+// scaffold up.  Only this level's entries are read: M levels cost the sum of their entries, not M scans of a table.
+__global__ void __launch_bounds__(256) k_level_sparse(const uint2 *cov_e, uint64_t n_cov, const uint2 *cv_e, uint64_t n_cv, const uint2 *cr_e,
+                                                      uint64_t n_cr, uint32_t n_pos, uint32_t *cov, float *cv, float *cr,
+                                                      const uint8_t *present, int n_seg, int M, int mm, Acc *acc)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t e_cv = n_cov + n_cv, total = e_cv + n_cr;
+    for (uint64_t s = t0; s < (uint64_t)n_seg; s += stride) acc[s].present = present[s * (uint64_t)M + (uint64_t)mm];
+    for (uint64_t i = t0; i < total; i += stride) {
+        if (i < n_cov) {
+            const uint2 e = cov_e[i];
+            if (e.x < n_pos) cov[e.x] += e.y;
+        } else if (i < e_cv) {
+            const uint2 e = cv_e[i - n_cov];
+            if (e.x < n_pos) cv[e.x] = __uint_as_float(e.y);
+        } else {
+            const uint2 e = cr_e[i - e_cv];
+            if (e.x < n_pos) cr[e.x] = __uint_as_float(e.y);
+        }
+    }
+}
+
+static void launch_level_sparse(const SummaryIn &in, int mm, uint32_t *cov, float *cv, float *cr, int n_seg, Acc *acc)
+{
+    const SparseLevels &sp = *in.sparse;
+    const uint2 *e[3];
+    uint64_t n[3];
+    for (int t = 0; t < 3; t++) {
+        const bool have = sp.pairs[t] != nullptr;
+        e[t] = have ? sp.pairs[t] + sp.off[t][mm] : nullptr;
+        n[t] = have ? (uint64_t)(sp.off[t][mm + 1] - sp.off[t][mm]) : 0;
+    }
+    const uint64_t work = std::max<uint64_t>(n[0] + n[1] + n[2], (uint64_t)n_seg);
+    const unsigned grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((work + 255) / 256, 1), 2048);
+    hipLaunchKernelGGL(k_level_sparse, dim3(grid), dim3(256), 0, in.stream, e[0], n[0], e[1], n[1], e[2], n[2], in.n_pos, cov, cv, cr,
+                       sp.cov_present, n_seg, in.M, mm, acc);
+}
+
+// One level onto the running arrays from whichever of the three sources `in` has: a stored profile's sparse series, a batch's dense
+// tables (its only level; overwrites) or its entry table.  The two additive sources need the arrays initialised before level 0.
+static inline bool source_is_dense(const SummaryIn &in) { return !in.sparse && in.M == 1; }
+
+static void launch_level(const SummaryIn &in, int mm, uint32_t *cov, float *cv, float *cr, const int64_t *d_bounds, int n_seg, Acc *acc)
+{
+    const dim3 blk(256);
+    if (in.sparse) launch_level_sparse(in, mm, cov, cv, cr, n_seg, acc);
+    else if (in.M == 1) launch_level_dense(in, dim3((in.n_pos + 255) / 256), blk, in.stream, in.n_pos, cov, cv, cr);
+    else hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, in.stream, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
+                            (uint32_t)mm, cov, cv, cr, d_bounds, n_seg, acc);
+}
+
 // segmented reductions: each lane walks a contiguous tile, keeps partials while the scaffold stays
 // the same and flushes them with atomics when it changes / at the end
 __global__ void __launch_bounds__(256) k_seg_reduce(const uint32_t *cov, const float *cv, const float *cr, uint32_t n_pos,
@@ -594,8 +650,9 @@ int run_summary(const SummaryIn &in, SummaryBuffers &B, isx_scaffold_level *host
     HIP_TRY(hipMemcpyAsync(B.bounds, in.scaffold_bounds, ((size_t)n_seg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(in.ev[0], s));
     Acc *acc = reinterpret_cast<Acc *>(B.acc);
-    const dim3 blk(256), gpos((n_pos + 255) / 256), gseg((n_seg + 255) / 256);
-    if (M > 1) {
+    const dim3 blk(256), gseg((n_seg + 255) / 256);
+    const bool dense = source_is_dense(in);
+    if (!dense) {
         HIP_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cv), 0x7FC00000, n_pos, s));
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cr), 0x7FC00000, n_pos, s));
@@ -636,15 +693,10 @@ int run_summary(const SummaryIn &in, SummaryBuffers &B, isx_scaffold_level *host
     };
     for (int mm = 0; mm < M; mm++) {
         hipLaunchKernelGGL(k_reset_acc, gseg, blk, 0, s, acc, n_seg);
-        if (M == 1) {
-            launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
-        } else {
-            hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0,
-                               in.n_ovf, (uint32_t)mm, B.cov, B.cv, B.cr, B.bounds, n_seg, acc);
-        }
+        launch_level(in, mm, B.cov, B.cv, B.cr, B.bounds, n_seg, acc);
         const uint32_t tiles = (n_pos + 63) / 64;
         hipLaunchKernelGGL(k_seg_reduce, dim3((tiles + 255) / 256), blk, 0, s, B.cov, B.cv, B.cr, n_pos, B.bounds, n_seg, acc,
-                           M == 1 ? 1 : 0);
+                           dense ? 1 : 0);
         if ((rc = sort_u32(B.cov, B.k_u32))) return rc;
         hipLaunchKernelGGL(k_pick_median<uint32_t>, gseg, blk, 0, s, B.k_u32, B.seg_off, n_seg, acc, 0, B.med);
         if ((rc = sort_f32(B.cv, B.k_f32))) return rc;
@@ -796,8 +848,9 @@ int run_gene_cov(const SummaryIn &in, SummaryBuffers &B, const std::vector<GeneW
     GC_TRY(hipMemcpyAsync(d_sb, in.scaffold_bounds, ((size_t)n_scaf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     if (n_work) GC_TRY(hipMemcpyAsync(d_work, work.data(), n_work * sizeof(GeneWork), hipMemcpyHostToDevice, s));
     GC_TRY(hipEventRecord(in.ev[0], s));
-    const dim3 blk(256), gpos((n_pos + 255) / 256), gseg((n_scaf + 255) / 256);
-    if (M > 1) {
+    const dim3 blk(256), gseg((n_scaf + 255) / 256);
+    const bool dense = source_is_dense(in);
+    if (!dense) {
         GC_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
         GC_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cv), 0x7FC00000, n_pos, s));
         GC_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cr), 0x7FC00000, n_pos, s));
@@ -805,12 +858,10 @@ int run_gene_cov(const SummaryIn &in, SummaryBuffers &B, const std::vector<GeneW
     for (int mm = 0; mm < M; mm++) {
         GC_TRY(hipMemsetAsync(d_sacc, 0, (size_t)n_scaf * sizeof(Acc), s));
         GC_TRY(hipMemsetAsync(d_any, 0, (size_t)n_scaf * sizeof(uint32_t), s));
-        if (M == 1) launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
-        else hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
-                                (uint32_t)mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
+        launch_level(in, mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
         launch_scaffold_any(s, B.cov, B.cv, n_pos, d_sb, n_scaf, d_any);
         launch_gene_cov(s, d_work, (uint32_t)n_work, B.cov, B.cv, M, mm, d_rows);
-        hipLaunchKernelGGL(k_gene_flags, gseg, blk, 0, s, d_any, d_sacc, n_scaf, mm, M, M == 1 ? 1 : 0, d_flags);
+        hipLaunchKernelGGL(k_gene_flags, gseg, blk, 0, s, d_any, d_sacc, n_scaf, mm, M, dense ? 1 : 0, d_flags);
     }
     GC_TRY(hipGetLastError());
     GC_TRY(hipEventRecord(in.ev[1], s));
@@ -856,16 +907,13 @@ int run_genome_cov(const SummaryIn &in, SummaryBuffers &B, const int32_t *scaffo
     GH_TRY(hipEventRecord(in.ev[0], s));
     GH_TRY(hipMemsetAsync(d_acc, 0, n_acc * sizeof(isx_genome_cov), s));
     GH_TRY(hipMemsetAsync(d_hist, 0, n_hist * sizeof(uint32_t), s));
-    const dim3 blk(256), gpos((n_pos + 255) / 256);
-    if (M > 1) {
+    if (!source_is_dense(in)) {
         GH_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
         GH_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cv), 0x7FC00000, n_pos, s));
         GH_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.cr), 0x7FC00000, n_pos, s));
     }
     for (int mm = 0; mm < M; mm++) {
-        if (M == 1) launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
-        else hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
-                                (uint32_t)mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
+        launch_level(in, mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
         launch_genome_hist(s, B.cov, n_pos, d_sb, d_sg, n_scaf, mask_edges, hist_bins, d_acc + mm, (size_t)M,
                            d_hist + (size_t)mm * hist_bins, (size_t)M * hist_bins);
     }
@@ -885,7 +933,7 @@ int run_irep_add(const SummaryIn &in, SummaryBuffers &B, const IrepAdd &a, float
 {
     hipStream_t s = in.stream;
     const uint32_t n_pos = in.n_pos;
-    const int n_scaf = in.n_scaffolds, M = in.M;
+    const int n_scaf = in.n_scaffolds;
     int rc;
     B.fit_positions(n_pos);
     if ((rc = dev_alloc(&B.cov, B.cap_pos)) || (rc = dev_alloc(&B.cv, B.cap_pos)) || (rc = dev_alloc(&B.cr, B.cap_pos))) return rc;
@@ -904,15 +952,9 @@ int run_irep_add(const SummaryIn &in, SummaryBuffers &B, const IrepAdd &a, float
     IR_TRY(hipMemcpyAsync(d_base, a.scaffold_base, (size_t)n_scaf * sizeof(int64_t), hipMemcpyHostToDevice, s));
     IR_TRY(hipMemsetAsync(d_sacc, 0, (size_t)n_scaf * sizeof(Acc), s));
     IR_TRY(hipEventRecord(in.ev[0], s));
-    const dim3 blk(256), gpos((n_pos + 255) / 256);
     if (a.level >= 0) {
-        if (M == 1) launch_level_dense(in, gpos, blk, s, n_pos, B.cov, B.cv, B.cr);
-        else {
-            IR_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
-            for (int mm = 0; mm <= a.level; mm++)
-                hipLaunchKernelGGL(k_level_apply, dim3(2048), blk, 0, s, in.entries, in.win_nent, in.slab, in.n_win, in.ovf0, in.n_ovf,
-                                   (uint32_t)mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
-        }
+        if (!source_is_dense(in)) IR_TRY(hipMemsetAsync(B.cov, 0, (size_t)n_pos * 4, s));
+        for (int mm = 0; mm <= a.level; mm++) launch_level(in, mm, B.cov, B.cv, B.cr, d_sb, n_scaf, d_sacc);
     }
     launch_irep_blocks(s, a.level >= 0 ? B.cov : nullptr, n_pos, d_sb, d_base, n_scaf, a.mask_edges, a.ref, a.ref_packed, a.ref_n,
                        a.block_cov, a.block_gc);

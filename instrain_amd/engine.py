@@ -415,6 +415,111 @@ class Batch:
             pass
 
 
+class StoredLevels:
+    """The covT / clonT / clonTR series of some scaffolds of a STORED profile on the device (isx_stored_*): `pack` is what
+    profile.stored.pack_levels returns, ref_codes (optional) the base codes of the pack's flat space for IRep.add_stored.
+    summarize / genome_coverage / profile_genes have the signatures and return values of Batch's methods, so gene_profile.profile_batch
+    and the genome roll-up run on either; level k of an output is pack["levels"][k].  A scaffold_bounds that is not the object's own
+    raises ValueError."""
+
+    MAX_HIST_BINS = Batch.MAX_HIST_BINS
+
+    def __init__(self, ctx, pack, ref_codes=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = None
+        self.bounds = np.ascontiguousarray(pack["bounds"], dtype=np.int64)
+        self.levels = np.ascontiguousarray(pack["levels"], dtype=np.int32)
+        if len(self.levels) > 1 and (self.levels[1:] <= self.levels[:-1]).any():
+            raise IsxError(-1, "StoredLevels: the pack's levels must ascend strictly")
+        self.scaffolds = list(pack.get("scaffolds", range(len(self.bounds) - 1)))
+        self.n_scaffolds, self.n_mm_bins = len(self.bounds) - 1, len(self.levels)
+        self.n_pos = int(self.bounds[-1])
+        n, L = self.n_scaffolds, self.n_mm_bins
+        self.cov_present = np.ascontiguousarray(pack["cov_present"], dtype=np.uint8)
+        self.clon_present = np.ascontiguousarray(pack.get("clon_present", np.zeros((n, L))), dtype=np.uint8)
+        if self.cov_present.shape != (n, L) or self.clon_present.shape != (n, L):
+            raise IsxError(-1, "StoredLevels: cov_present / clon_present must be [n_scaffolds, n_levels]")
+        args, keep = [], [self.cov_present, self.clon_present]
+        for short, vdt in (("cov", np.uint32), ("clon", np.float32), ("clonr", np.float32)):
+            if pack.get(short + "_offsets") is None:
+                args += [None, None, None]
+                continue
+            off = np.ascontiguousarray(pack[short + "_offsets"], dtype=np.int64)
+            gp = np.ascontiguousarray(pack[short + "_gpos"], dtype=np.uint32)
+            val = np.ascontiguousarray(pack[short + "_values"], dtype=vdt)
+            if len(off) != L + 1 or len(gp) != len(val) or (len(off) and off[-1] != len(gp)):
+                raise IsxError(-1, "StoredLevels: %s_offsets must have n_levels + 1 entries and end at the number of %s_gpos / %s_values"
+                               % (short, short, short))
+            keep += [off, gp, val]
+            args += [off.ctypes.data, gp.ctypes.data if len(gp) else None, val.ctypes.data if len(val) else None]
+        ref = None
+        if ref_codes is not None:
+            ref = np.ascontiguousarray(ref_codes, dtype=np.uint8)
+            if len(ref) != self.n_pos:
+                raise IsxError(-1, "StoredLevels: ref_codes must hold one code per flat position (%d)" % self.n_pos)
+        self.has_ref = ref is not None
+        h = C.c_void_p()
+        check(self.lib.isx_stored_create(ctx.h, n, self.bounds.ctypes.data, L, self.cov_present.ctypes.data, self.clon_present.ctypes.data,
+                                         *args, ref.ctypes.data if ref is not None else None, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def _own_bounds(self, scaffold_bounds, who):
+        if scaffold_bounds is not None and not np.array_equal(np.asarray(scaffold_bounds, dtype=np.int64), self.bounds):
+            raise ValueError("StoredLevels.%s: scaffold_bounds are not the object's own" % who)
+
+    def summarize(self, scaffold_bounds=None):
+        """as Batch.summarize -> (SCAFFOLD_LEVEL_DT [n_scaffolds, n_levels], device ms)"""
+        self._own_bounds(scaffold_bounds, "summarize")
+        out = np.zeros((self.n_scaffolds, self.n_mm_bins), dtype=_lib.SCAFFOLD_LEVEL_DT)
+        ms = C.c_float(0)
+        check(self.lib.isx_stored_summarize(self.h, out.ctypes.data, C.byref(ms)))
+        return out, ms.value
+
+    def genome_coverage_raw(self, scaffold_bounds, scaffold_genome, n_genomes, mask_edges=100, hist_bins=4096):
+        self._own_bounds(scaffold_bounds, "genome_coverage")
+        sg = np.ascontiguousarray(scaffold_genome, dtype=np.int32)
+        if len(sg) != self.n_scaffolds:
+            raise IsxError(-1, "genome_coverage: one genome id per scaffold")
+        acc = np.zeros((max(int(n_genomes), 1), self.n_mm_bins), dtype=_lib.GENOME_COV_DT)
+        hist = np.zeros((max(int(n_genomes), 1), self.n_mm_bins, max(int(hist_bins), 1)), dtype=np.uint32)
+        ms = C.c_float(0)
+        check(self.lib.isx_stored_genome_coverage(self.h, sg.ctypes.data, int(n_genomes), int(mask_edges), int(hist_bins), acc.ctypes.data,
+                                                  hist.ctypes.data, C.byref(ms)))
+        return acc, hist, ms.value
+
+    genome_coverage = Batch.genome_coverage         # the same retry with more bins, on genome_coverage_raw above
+
+    def profile_genes(self, genes, scaffold_bounds, gene_first, gene_last):
+        """as Batch.profile_genes -> (GENE_COV_DT rows [n_call_genes, n_levels], scaffold flags [n_scaffolds, n_levels], device ms)"""
+        self._own_bounds(scaffold_bounds, "profile_genes")
+        gf = np.ascontiguousarray(gene_first, dtype=np.int32)
+        gl = np.ascontiguousarray(gene_last, dtype=np.int32)
+        if len(gf) != self.n_scaffolds or len(gl) != self.n_scaffolds:
+            raise IsxError(-1, "profile_genes: one gene range per scaffold")
+        n_call = int((gl - gf).sum())
+        rows = np.zeros((max(n_call, 1), self.n_mm_bins), dtype=_lib.GENE_COV_DT)
+        flags = np.zeros((self.n_scaffolds, self.n_mm_bins), dtype=np.uint8)
+        ms = C.c_float(0)
+        check(self.lib.isx_stored_profile_genes(self.h, genes.h, gf.ctypes.data, gl.ctypes.data, rows.ctypes.data, flags.ctypes.data,
+                                                C.byref(ms)))
+        # the device's GENE_LEVEL_PRESENT is the covT key; a level that is a key of covT but not of the scaffold's clonT gives no
+        # clonality rows (elsewhere the bits stay as a live batch's are)
+        flags[(self.cov_present != 0) & (self.clon_present == 0)] &= np.uint8(0xFF ^ _lib.GENE_CLON_ANY)
+        return rows[:n_call], flags, ms.value
+
+    def close(self):
+        if self.h:
+            self.lib.isx_stored_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def snv_level_counts(ctx, rows, scaffold_bounds, n_levels):
     """calc_snps of every (scaffold, level) at once (isx_snv_level_counts) on SNV_DT rows in (gpos, mm) order
     -> (SNV_LEVEL_DT [n_scaffolds, n_levels], device ms)"""
@@ -536,6 +641,16 @@ class IRep:
             raise IsxError(-1, "IRep.add: one set index per scaffold")
         ms = C.c_float(0)
         check(self.lib.isx_irep_add(self.h, batch.h, len(sb) - 1, sb.ctypes.data, si.ctypes.data, int(level), C.byref(ms)))
+        return ms.value
+
+    def add_stored(self, stored, set_index, level):
+        """add() for a StoredLevels object created with ref_codes: set_index[i] = which of the accumulator's scaffolds the object's
+        scaffold i is (-1: none); level as for add() -> device ms"""
+        si = np.ascontiguousarray(set_index, dtype=np.int32)
+        if len(si) != stored.n_scaffolds:
+            raise IsxError(-1, "IRep.add_stored: one set index per scaffold")
+        ms = C.c_float(0)
+        check(self.lib.isx_irep_add_stored(self.h, stored.h, si.ctypes.data, int(level), C.byref(ms)))
         return ms.value
 
     def blocks(self):

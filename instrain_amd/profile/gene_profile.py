@@ -312,6 +312,39 @@ def profile_batch(batch, gs, scaffolds, bounds, snv_table, mm_values=None, log_l
     return tables
 
 
+def profile_genes_stored(ctx, profile, genes, scaffold2length, max_positions=1 << 27, log_lines=None):
+    """`inStrain profile_genes -i IS -g genes.fna` (GeneProfile.calculate_gene_metrics on the stored covT / clonT /
+    cumulative_snv_table): the five gene tables exactly as profile_bam(gene_tables=) fills them -- genes_table included, the
+    GeneException rule of profile_batch kept.  profile: what stored.load_profile returns; genes: a gene file path,
+    (scaff2geneinfo, scaff2gene2sequence) or a GeneSet; scaffold2length: name -> length, whose order is the order of the rows.
+    Works in chunks of whole scaffolds of at most max_positions flat positions (a longer scaffold goes alone); only scaffolds
+    that have genes are packed.  Per chunk: stored.pack_levels -> engine.StoredLevels -> profile_batch."""
+    from . import stored
+    if isinstance(genes, str):
+        genes = parse_genes(genes)
+    gs = genes if isinstance(genes, GeneSet) else GeneSet(ctx, *genes)
+    log = log_lines if log_lines is not None else []
+    try:
+        names = [s for s in scaffold2length if s in gs.gdb]
+        levels = stored.profile_levels(profile)
+        sdb = profile.get("cumulative_snv_table")
+        sdb = pd.DataFrame() if sdb is None else sdb
+        parts = {k: [] for k in TABLE_NAMES}
+        for cn, _, pack, st in stored.level_chunks(ctx, profile, names, [scaffold2length[s] for s in names], levels, max_positions):
+            cdb = sdb[sdb['scaffold'].astype(object).isin(set(cn))] if len(sdb) else sdb
+            gt = profile_batch(st, gs, cn, pack["bounds"], cdb, np.asarray(levels, dtype=np.int64), log)
+            for k in TABLE_NAMES:
+                parts[k].append(gt[k])
+        out = {'genes_table': genes_table(gs.gdb)}
+        for k in TABLE_NAMES:
+            kept = [d for d in parts[k] if len(d)]
+            out[k] = pd.concat(kept).reset_index(drop=True) if kept else pd.DataFrame()
+        return out
+    finally:
+        if gs is not genes:
+            gs.close()
+
+
 def gene_info(tables, genes_table):
     """SNVprofile.generate('gene_info'): the highest-mm row of every gene from genes_coverage, genes_clonality and genes_SNP_count
     joined onto genes_table, without N_sites / S_sites, columns ordered, genes with coverage > 0"""

@@ -66,6 +66,73 @@ def _order_statistic(cum, k):
     return (cum > k[..., None]).argmax(axis=-1)
 
 
+def _fasta_codes(fasta):
+    """name -> base codes of a scaffold: `fasta` is a path or a dict name -> sequence"""
+    from .. import engine
+    if isinstance(fasta, dict):
+        seqs = fasta
+    else:
+        from .gene_profile import _fasta_records
+        seqs = {name: seq for name, _, seq in _fasta_records(fasta)}
+    return lambda name: engine.encode_seq(str(seqs[name]).upper())
+
+
+def genome_wide_stored(ctx, profile, stb, scaffold2length, fasta=None, mapping_info=None, skip_mm_profiling=False,
+                       max_positions=1 << 27, irep=True, scaffold_tables=None, irep_blocks=None):
+    """`inStrain genome_wide -i IS -s stb` (genomeLevel_from_IS :145-269 on the stored covT, scaffold table and raw_linkage_table):
+    {"genome_info", "scaffold2bin", "bin2length"} as profile_bam(genome_tables=) returns them.  profile: what stored.load_profile
+    returns; scaffold2length: name -> length of the run's scaffolds, all of which are laid out, in chunks of whole scaffolds of at most
+    max_positions flat positions (a longer scaffold goes alone; a genome may be cut).  Per chunk: StoredLevels.summarize,
+    engine.snv_level_counts on the stored SNV table, engine.ld_level_sums on the stored raw_linkage_table, StoredLevels.genome_coverage,
+    IRep.add_stored when `fasta` (a path, or name -> sequence) is given and `irep` is true -- otherwise the iRep columns are NaN --
+    then GenomeTables.add_batch.  mapping_info: the run's mapping_info for the reads_* columns.  scaffold_tables: a dict that receives
+    every scaffold's cumulative_scaffold_table; irep_blocks: a list that receives IRep.blocks() before the fit."""
+    from .. import engine
+    from . import stored
+    from .profile_utilities import make_coverage_table
+    s2l = {n: int(v) for n, v in dict(scaffold2length).items()}
+    names = list(s2l)
+    genomes = GenomeTables(stb, s2l)
+    levels = stored.profile_levels(profile)
+    mms = np.asarray(levels, dtype=np.int64)
+    acc_irep, irep_index = None, {}
+    if fasta is not None and irep:
+        i_names, i_lengths, i_genome = genomes.irep_scaffolds()
+        if i_names:
+            acc_irep = engine.IRep(ctx, i_lengths, i_genome, len(genomes.genomes), mask_edges=genomes.mask_edges)
+            irep_index = {name: i for i, name in enumerate(i_names)}
+    try:
+        ref_of = _fasta_codes(fasta) if acc_irep is not None else None
+        for cn, cl, pack, st in stored.level_chunks(ctx, profile, names, [s2l[n] for n in names], levels, max_positions, ref_of):
+            sb = pack["bounds"]
+            rows, _ = st.summarize(sb)
+            rows["mm"] = mms[rows["mm"].astype(np.int64)]
+            offsets = dict(zip(cn, sb[:-1].tolist()))
+            snv_levels, _ = engine.snv_level_counts(ctx, stored.snv_rows(profile.get("cumulative_snv_table"), offsets, levels), sb, len(levels))
+            ld_levels, _ = engine.ld_level_sums(ctx, stored.ld_rows(profile.get("raw_linkage_table"), offsets, levels), sb, len(levels))
+            ids, local = genomes.batch_genomes(cn)
+            acc = hist = None
+            if local:
+                acc, hist, _ = st.genome_coverage(sb, ids, len(local), mask_edges=genomes.mask_edges)
+            if acc_irep is not None:
+                acc_irep.add_stored(st, [irep_index.get(n, -1) for n in cn], genomes.irep_level(mms, len(levels), skip_mm_profiling))
+            genomes.add_batch(cn, cl, rows, snv_levels, ld_levels, local, acc, hist, mms=mms)
+            if scaffold_tables is not None:
+                for j, n in enumerate(cn):
+                    scaffold_tables[n] = make_coverage_table(rows[j], cl[j], n, None, snv_levels[j])
+        if acc_irep is not None:
+            if irep_blocks is not None:
+                irep_blocks.append(acc_irep.blocks())
+            genomes.set_irep(acc_irep.finish()[0])
+        if mapping_info is not None:
+            genomes.set_mapping_info(mapping_info)
+        return {"genome_info": genomes.genome_info(skip_mm_profiling=skip_mm_profiling), "scaffold2bin": genomes.stb,
+                "bin2length": genomes.bin2length}
+    finally:
+        if acc_irep is not None:
+            acc_irep.close()
+
+
 class GenomeTables:
     """genome_info of a run, merged batch by batch.
 
