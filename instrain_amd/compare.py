@@ -51,6 +51,37 @@ def calc_mm2overlap(batch1, batch2, scaffold_bounds, min_cov=5):
     return mm2overlap, mm2coverage, ms.value
 
 
+def _comparison_row(r, length, scaffold, name1, name2):
+    """one COMPARE_LEVEL_DT record as the reference's comparisonsTable row (readComparer.py:437-502); the key order is the column order
+    of every frame built from these rows"""
+    bases = int(r["both"])
+    snps, popsnps = int(r["consensus_snps"]), int(r["population_snps"])
+    return {"mm": int(r["mm"]), "scaffold": scaffold, "name1": name1, "name2": name2,
+            "coverage_overlap": r["both"] / r["either"] if r["either"] > 0 else 0,
+            "compared_bases_count": bases, "percent_genome_compared": bases / length, "length": length,
+            "consensus_SNPs": snps, "population_SNPs": popsnps,
+            "conANI": (bases - snps) / bases if bases else np.nan,
+            "popANI": (bases - popsnps) / bases if bases else np.nan}
+
+
+def _mdb(raw, offsets, failed):
+    """COMPARE_SNP_DT rows as the Mdb dict: offsets = first gpos of every scaffold (ascending); rows on `failed` scaffolds are left out"""
+    scaf = np.searchsorted(offsets, raw["gpos"].astype(np.int64), side="right") - 1
+    if failed:
+        ok = ~np.isin(scaf, sorted(failed))
+        raw, scaf = raw[ok], scaf[ok]
+    return {"raw": raw, "scaffold": scaf, "position": raw["gpos"].astype(np.int64) - offsets[scaf]}
+
+
+def _batch_args(who, index, batch_scaffold_names, batch_bounds):
+    """-> (bounds int64, ids int32: scaffold of the set or -1) of a batch handed to a SampleSet; `who` heads the ValueError"""
+    bb = np.ascontiguousarray(batch_bounds, dtype=np.int64)
+    ids = np.array([index.get(n, -1) for n in batch_scaffold_names], dtype=np.int32)
+    if len(bb) != len(ids) + 1:
+        raise ValueError("%s: batch_bounds has one entry more than the batch has scaffolds" % who)
+    return bb, ids
+
+
 BASES = np.array(["A", "C", "T", "G", "N"])
 POOL_CLASSES = ("DivergentSite", "SNS", "SNV", "con_SNV", "pop_SNV")        # the <class>_count columns of PMdb (polymorpher.py:492)
 
@@ -81,24 +112,13 @@ def compare_scaffolds(batch1, batch2, scaffold_bounds, scaffold_names=None, name
         for r in rows:
             if not (r["present_a"] or r["present_b"]):
                 continue
-            bases = int(r["both"])
-            snps, popsnps = int(r["consensus_snps"]), int(r["population_snps"])
-            table.append({"mm": int(r["mm"]), "scaffold": names[i], "name1": name1, "name2": name2,
-                          "coverage_overlap": r["both"] / r["either"] if r["either"] > 0 else 0,
-                          "compared_bases_count": bases, "percent_genome_compared": bases / mLen, "length": mLen,
-                          "consensus_SNPs": snps, "population_SNPs": popsnps,
-                          "conANI": (bases - snps) / bases if bases else np.nan,
-                          "popANI": (bases - popsnps) / bases if bases else np.nan})
+            table.append(_comparison_row(r, mLen, names[i], name1, name2))
     mdb = None
     if store_mismatch_locations:
         raw = np.zeros(n_rows.value, dtype=_lib.COMPARE_SNP_DT)
         if n_rows.value:
             check(batch1.lib.isx_compare_fetch_snps(batch1.h, raw.ctypes.data))
-        scaf = np.searchsorted(sb, raw["gpos"].astype(np.int64), side="right") - 1
-        if failed:
-            ok = ~np.isin(scaf, sorted(failed))
-            raw, scaf = raw[ok], scaf[ok]
-        mdb = {"raw": raw, "scaffold": scaf, "position": raw["gpos"].astype(np.int64) - sb[scaf]}
+        mdb = _mdb(raw, sb, failed)
     return table, mdb, ms.value
 
 
@@ -353,10 +373,7 @@ class SampleSet:
         """what `batch` (a run Batch or a collected pipe slot) holds of the sample; scaffolds the set does not name are skipped.
         mm_values: the real mm of every device level (profile_bam's mm_values), None = level k is mm k.  The batch may be closed /
         its slot released as soon as this returns."""
-        bb = np.ascontiguousarray(batch_bounds, dtype=np.int64)
-        ids = np.array([self.index.get(n, -1) for n in batch_scaffold_names], dtype=np.int32)
-        if len(bb) != len(ids) + 1:
-            raise ValueError("add_batch: batch_bounds has one entry more than the batch has scaffolds")
+        bb, ids = _batch_args("add_batch", self.index, batch_scaffold_names, batch_bounds)
         mmv = None if mm_values is None else np.ascontiguousarray(mm_values, dtype=np.int32)
         if mmv is not None and len(mmv) != batch.n_mm_bins:
             raise ValueError("add_batch: one mm value per level of the batch")
@@ -455,16 +472,8 @@ class SampleSet:
         present[failed] = False
         table = []
         for sc, p, a in np.argwhere(present):
-            r, mLen = by_scaffold[sc, p, a], int(self.lengths[sc])
-            bases = int(r["both"])
-            snps, popsnps = int(r["consensus_snps"]), int(r["population_snps"])
-            table.append({"mm": int(r["mm"]), "scaffold": self.names[sc], "name1": self.samples[pairs[p][0]],
-                          "name2": self.samples[pairs[p][1]],
-                          "coverage_overlap": r["both"] / r["either"] if r["either"] > 0 else 0,
-                          "compared_bases_count": bases, "percent_genome_compared": bases / mLen, "length": mLen,
-                          "consensus_SNPs": snps, "population_SNPs": popsnps,
-                          "conANI": (bases - snps) / bases if bases else np.nan,
-                          "popANI": (bases - popsnps) / bases if bases else np.nan})
+            table.append(_comparison_row(by_scaffold[sc, p, a], int(self.lengths[sc]), self.names[sc], self.samples[pairs[p][0]],
+                                         self.samples[pairs[p][1]]))
         return table
 
     def mismatch_locations(self, name1, name2):
@@ -479,11 +488,7 @@ class SampleSet:
         raw = np.zeros(n.value, dtype=_lib.COMPARE_SNP_DT)
         if n.value:
             check(self.lib.isx_cmpset_fetch_snps(self.h, raw.ctypes.data))
-        scaf = np.searchsorted(self.offsets, raw["gpos"].astype(np.int64), side="right") - 1
-        if self.failed:
-            ok = ~np.isin(scaf, sorted(self.failed))
-            raw, scaf = raw[ok], scaf[ok]
-        return {"raw": raw, "scaffold": scaf, "position": raw["gpos"].astype(np.int64) - self.offsets[scaf]}
+        return _mdb(raw, self.offsets, self.failed)
 
     # ---- SNV pooling (polymorpher.py PoolController; include/instrain_amd.h isx_cmpset_pool_*) ----
     def pool_sites(self):
@@ -503,10 +508,7 @@ class SampleSet:
     def pool_add(self, sample_name, batch, batch_scaffold_names, batch_bounds):
         """the all-level base counts of `batch` at the sites the sample does not own (get_pooling_counts); arguments as add_batch.  A
         one-level pipe slot needs the pipe's want_counts.  The batch may be closed / its slot released as soon as this returns."""
-        bb = np.ascontiguousarray(batch_bounds, dtype=np.int64)
-        ids = np.array([self.index.get(n, -1) for n in batch_scaffold_names], dtype=np.int32)
-        if len(bb) != len(ids) + 1:
-            raise ValueError("pool_add: batch_bounds has one entry more than the batch has scaffolds")
+        bb, ids = _batch_args("pool_add", self.index, batch_scaffold_names, batch_bounds)
         if sample_name not in self.samples:
             raise ValueError("pool_add: sample %r was never added" % (sample_name,))
         check(self.lib.isx_cmpset_pool_add(self.h, self.samples.index(sample_name), batch.h, len(ids), bb.ctypes.data, ids.ctypes.data))

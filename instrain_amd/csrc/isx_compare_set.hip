@@ -13,7 +13,7 @@
 //   prows[]               (after isx_cmpset_pool_enable) the highest-mm row that is not cryptic: SNV pooling, isx_compare_pool.hip
 // so a batch can go as soon as it has been added.  A sample's STORED profile (covT, cumulative_snv_table: compare_controller.py:520-577)
 // leaves the same three through isx_cmpset_add_profile: k_profile_planes turns the sparse covT series into the planes without a dense
-// coverage array, the SNV tail (reserve_last_rows / launch_last_rows) is shared with isx_cmpset_add.  The set's position space starts every scaffold on a 64-position word
+// coverage array, the SNV tail (reserve_snv_tail / launch_rows) is shared with isx_cmpset_add.  The set's position space starts every scaffold on a 64-position word
 // (cmpset_layout.cpp): no word belongs to two scaffolds, `both` of a pair is popcount(a & b) word by word.
 // Everything counted here is an integer; sums go through 64-bit integer atomics, so a call's bytes do not depend on timing.
 #include <algorithm>
@@ -23,6 +23,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "isx_compare_set.h"
+#include "isx_snp_rules.h"
 
 using namespace isxset;
 
@@ -57,7 +58,9 @@ __global__ void __launch_bounds__(256) k_pack_plane(const uint32_t *cov, uint32_
     if (lane == 0 && dw >= 0 && dw < n_words) plane[dw] = mask;
 }
 
-// (set position, mm) keys of a batch's SNV rows; rows of scaffolds the set does not name get the all-ones key (sorted last)
+// (set position, mm) keys of a batch's SNV rows; rows of scaffolds the set does not name get the all-ones key (sorted last).
+// POOL: the pooling keys (polymorpher.py:65-68) -- the same, with cryptic rows keyed out as well
+template <bool POOL>
 __global__ void k_set_keys(const isx_snv *snv, uint32_t n, const int64_t *bbounds, int n_bscaf, const int64_t *set_pos0, uint64_t *keys,
                            uint32_t *idx)
 {
@@ -66,18 +69,21 @@ __global__ void k_set_keys(const isx_snv *snv, uint32_t n, const int64_t *bbound
     const int64_t g = snv[i].gpos;
     const int sc = seg_of(bbounds, n_bscaf, g);
     const int64_t p0 = set_pos0[sc];
-    const bool in = p0 >= 0 && g >= bbounds[sc] && g < bbounds[sc + 1];
+    const bool in = p0 >= 0 && g >= bbounds[sc] && g < bbounds[sc + 1] && !(POOL && snv[i].cryptic);
     keys[i] = in ? ((uint64_t)(p0 + (g - bbounds[sc])) << 16) | snv[i].mm : ~0ull;
     idx[i] = i;
 }
 
-// the same keys for the rows of a stored cumulative_snv_table: the scaffold is named, not found (the host has checked every field)
-__global__ void k_profile_keys(const isx_profile_snv *snv, uint32_t n, const int64_t *set_pos0, int n_cscaf, uint64_t *keys, uint32_t *idx)
+// the same keys for the rows of a stored cumulative_snv_table: the scaffold is named, not found (the host has checked every field).
+// A stored row has no class / cryptic fields, they come beside it (snv_flags: bits 0..2 class, bit 3 cryptic; NULL unless POOL)
+template <bool POOL>
+__global__ void k_profile_keys(const isx_profile_snv *snv, const uint8_t *snv_flags, uint32_t n, const int64_t *set_pos0, int n_cscaf,
+                               uint64_t *keys, uint32_t *idx)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int32_t sc = snv[i].scaffold;
-    const int64_t p0 = sc >= 0 && sc < n_cscaf ? set_pos0[sc] : -1;
+    const int64_t p0 = sc >= 0 && sc < n_cscaf && !(POOL && (snv_flags[i] & 8)) ? set_pos0[sc] : -1;
     keys[i] = p0 >= 0 ? ((uint64_t)(p0 + snv[i].position) << 16) | (uint32_t)(snv[i].mm & 0xFFFF) : ~0ull;
     idx[i] = i;
 }
@@ -138,66 +144,35 @@ __global__ void k_last_flags(const uint64_t *keys, uint32_t n, uint32_t *flags)
     flags[i] = keys[i] != ~0ull && (i + 1 == n || (keys[i + 1] >> 16) != (keys[i] >> 16)) ? 1u : 0u;
 }
 
-// the flagged rows, in key order, behind the sample's earlier rows; total[0] = how many.  Src: isx_snv (a resident batch) or
-// isx_profile_snv (a stored cumulative_snv_table) -- both name the payload fields alike
-template <class Src>
-__global__ void k_gather_last(const uint64_t *keys, const uint32_t *idx, const uint32_t *flags, const uint32_t *pos, uint32_t n,
-                              const Src *snv, CsRow *out, uint32_t cap, uint32_t *total)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (i + 1 == n) total[0] = pos[i] + flags[i];
-    if (!flags[i] || pos[i] >= cap) return;
-    const Src x = snv[idx[i]];
-    CsRow r;
-    r.gpos = (uint32_t)(keys[i] >> 16);
-    r.con_base = x.con_base; r.ref_base = x.ref_base; r.var_base = x.var_base; r.allele_count = x.allele_count;
-    for (int k = 0; k < 4; k++) r.cnt[k] = x.cnt[k];
-    out[pos[i]] = r;
-}
-
-// the pooling keys (polymorpher.py:65-68): the same, with cryptic rows keyed out as well
-__global__ void k_pool_keys(const isx_snv *snv, uint32_t n, const int64_t *bbounds, int n_bscaf, const int64_t *set_pos0, uint64_t *keys,
-                            uint32_t *idx)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t g = snv[i].gpos;
-    const int sc = seg_of(bbounds, n_bscaf, g);
-    const int64_t p0 = set_pos0[sc];
-    const bool in = p0 >= 0 && g >= bbounds[sc] && g < bbounds[sc + 1] && !snv[i].cryptic;
-    keys[i] = in ? ((uint64_t)(p0 + (g - bbounds[sc])) << 16) | snv[i].mm : ~0ull;
-    idx[i] = i;
-}
-
-// the stored-record twin: a stored row has no class / cryptic fields, they come beside it (snv_flags: bits 0..2 class, bit 3 cryptic)
-__global__ void k_profile_pool_keys(const isx_profile_snv *snv, const uint8_t *snv_flags, uint32_t n, const int64_t *set_pos0, int n_cscaf,
-                                    uint64_t *keys, uint32_t *idx)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t sc = snv[i].scaffold;
-    const int64_t p0 = sc >= 0 && sc < n_cscaf && !(snv_flags[i] & 8) ? set_pos0[sc] : -1;
-    keys[i] = p0 >= 0 ? ((uint64_t)(p0 + snv[i].position) << 16) | (uint32_t)(snv[i].mm & 0xFFFF) : ~0ull;
-    idx[i] = i;
-}
-
 __device__ __forceinline__ uint8_t class_of(const isx_snv &x, const uint8_t *, uint32_t) { return x.cls; }
 __device__ __forceinline__ uint8_t class_of(const isx_profile_snv &, const uint8_t *snv_flags, uint32_t i) { return snv_flags[i] & 7; }
 
-// Src: isx_snv (snv_flags unused) or isx_profile_snv with its snv_flags
+// what a compare row / a pool row keeps of source row i besides its position and counts
 template <class Src>
-__global__ void k_gather_pool(const uint64_t *keys, const uint32_t *idx, const uint32_t *flags, const uint32_t *pos, uint32_t n,
-                              const Src *snv, const uint8_t *snv_flags, PoolRow *out, uint32_t cap, uint32_t *total)
+__device__ __forceinline__ void fill_row(CsRow &r, const Src &x, const uint8_t *, uint32_t)
+{
+    r.con_base = x.con_base; r.ref_base = x.ref_base; r.var_base = x.var_base; r.allele_count = x.allele_count;
+}
+template <class Src>
+__device__ __forceinline__ void fill_row(PoolRow &r, const Src &x, const uint8_t *snv_flags, uint32_t i)
+{
+    r.con_base = x.con_base; r.ref_base = x.ref_base; r.cls = class_of(x, snv_flags, i); r.pad = 0;
+}
+
+// the flagged rows, in key order, behind the sample's earlier rows; total[0] = how many.  Src: isx_snv (a resident batch; snv_flags
+// unused) or isx_profile_snv (a stored cumulative_snv_table; its snv_flags when Row is PoolRow) -- both name the payload fields alike
+template <class Src, class Row>
+__global__ void k_gather_last(const uint64_t *keys, const uint32_t *idx, const uint32_t *flags, const uint32_t *pos, uint32_t n,
+                              const Src *snv, const uint8_t *snv_flags, Row *out, uint32_t cap, uint32_t *total)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (i + 1 == n) total[0] = pos[i] + flags[i];
     if (!flags[i] || pos[i] >= cap) return;
     const Src x = snv[idx[i]];
-    PoolRow r;
+    Row r;
     r.gpos = (uint32_t)(keys[i] >> 16);
-    r.con_base = x.con_base; r.ref_base = x.ref_base; r.cls = class_of(x, snv_flags, idx[i]); r.pad = 0;
+    fill_row(r, x, snv_flags, idx[i]);
     for (int k = 0; k < 4; k++) r.cnt[k] = x.cnt[k];
     out[pos[i]] = r;
 }
@@ -265,24 +240,13 @@ __device__ __forceinline__ int64_t row_of(const CsRow *rows, uint32_t n, uint32_
     return lo < n && rows[lo].gpos == gpos ? (int64_t)lo : -1;
 }
 
-// readComparer.py:306-315 is_present (as in isx_summary.hip)
-__device__ __forceinline__ bool is_present(uint32_t count, uint32_t total, const uint8_t *lut, int32_t lut_n, int32_t fallback,
-                                           double min_freq)
-{
-    int32_t min_bases = fallback;
-    if (total < (uint32_t)lut_n && lut[total] != 255) min_bases = lut[total];
-    return (int64_t)count >= (int64_t)min_bases && ((double)count / (double)total) >= min_freq;
-}
-
 struct SnpArgs {
     const CsRow *const *rows;           // [S] last-row tables
     const uint32_t *n_rows;             // [S]
     const SnpPair *pairs;               // the launch's pairs
     const uint64_t *cand_off;           // [n_pairs + 1]: prefix of n_rows[i] + n_rows[j]
     int n_pairs;
-    const uint8_t *lut;
-    int32_t lut_n, fallback;
-    double min_freq;
+    isxsnp::NullModel nm;
     const uint64_t *const *planes;
     const int16_t *lmap;
     int A;
@@ -298,8 +262,8 @@ struct SnpArgs {
     uint32_t *cursor, cap_rows;
 };
 
-// SNP half, one thread per (pair, row of either sample): k_snp_candidates' rules (isx_summary.hip) on the two samples' last-row
-// tables, then per axis level the two planes' bits at the position
+// SNP half, one thread per (pair, row of either sample): the verdict of isx_snp_rules.h on the two samples' last-row tables, then
+// per axis level the two planes' bits at the position
 __global__ void __launch_bounds__(256) k_cmpset_snp(const SnpArgs a)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -325,26 +289,19 @@ __global__ void __launch_bounds__(256) k_cmpset_snp(const SnpArgs a)
     for (int k = 0; k < a.A; k++) { has_a |= pa[k] != 0; has_b |= pb[k] != 0; }
     if (!has_a || !has_b) return;                                           // the pair is not compared on this scaffold (cur_names)
     CsRow y = x;                        // the other sample's row when both have one
-    bool con, pop;
+    uint32_t verdict;
     if (j < 0) {                        // the row exists in one sample only (the other's columns are NaN)
-        con = x.con_base != x.ref_base;                                     // call_con_snps :296-301
-        if (x.ref_base > 3) {           // '{ref_base}_2' with ref_base N: the reference raises KeyError
+        verdict = isxsnp::snp_verdict(x, (const CsRow *)nullptr, a.nm);
+        if (verdict == isxsnp::SNP_REF_FAILS) {
             atomicOr(&a.failed[(size_t)pr.out * a.n_scaf + sc], 1u);
             return;
         }
-        const uint32_t total = x.cnt[0] + x.cnt[1] + x.cnt[2] + x.cnt[3];
-        pop = !is_present(x.cnt[x.ref_base], total, a.lut, a.lut_n, a.fallback, a.min_freq);     // call_pop_snps :329-344
     } else {
         y = rb[j];                      // (from_a holds here)
-        con = x.con_base != y.con_base;                                     // :304
-        const uint32_t ta = x.cnt[0] + x.cnt[1] + x.cnt[2] + x.cnt[3], tb = y.cnt[0] + y.cnt[1] + y.cnt[2] + y.cnt[3];
-        if (!con) pop = false;                                                                              // :325
-        else if (is_present(y.cnt[x.con_base & 3], tb, a.lut, a.lut_n, a.fallback, a.min_freq)) pop = false;   // :349-355
-        else if (is_present(x.cnt[y.con_base & 3], ta, a.lut, a.lut_n, a.fallback, a.min_freq)) pop = false;   // :358-361
-        else if (x.allele_count > 1 && y.allele_count > 1 && x.var_base == y.var_base) pop = false;         // :364-367
-        else pop = true;
+        verdict = isxsnp::snp_verdict(x, &y, a.nm);
     }
-    if (!con && !pop) return;                                               // "Only keep SNPs" :281
+    if (!verdict) return;                                                   // "Only keep SNPs" :281
+    const bool con = verdict & isxsnp::SNP_CON, pop = verdict & isxsnp::SNP_POP;
     const int64_t word = x.gpos >> 6;
     if (word >= a.n_words) return;
     const uint64_t bit = 1ull << (x.gpos & 63);
@@ -365,14 +322,8 @@ __global__ void __launch_bounds__(256) k_cmpset_snp(const SnpArgs a)
         r.consensus_snp = con ? 1 : 0; r.population_snp = pop ? 1 : 0;
         const bool row_a = from_a, row_b = !from_a || j >= 0;
         const CsRow &xa = x, &xb = from_a ? y : x;
-        if (row_a) {
-            r.has_a = 1; r.con_a = xa.con_base; r.ref_a = xa.ref_base; r.var_a = xa.var_base;
-            for (int q = 0; q < 4; q++) r.cnt_a[q] = xa.cnt[q];
-        }
-        if (row_b) {
-            r.has_b = 1; r.con_b = xb.con_base; r.ref_b = xb.ref_base; r.var_b = xb.var_base;
-            for (int q = 0; q < 4; q++) r.cnt_b[q] = xb.cnt[q];
-        }
+        if (row_a) isxsnp::snp_fill_side<false>(r, xa);
+        if (row_b) isxsnp::snp_fill_side<true>(r, xb);
         a.out_rows[at] = r;
     }
 }
@@ -407,33 +358,50 @@ int level_axis(const isx_cmpset *st, std::vector<int32_t> &axis, int32_t *n_axis
     return isx_cmpset_level_map(S, n_levels.data(), all.data(), ISX_CMPSET_MAX_LEVELS, axis.data(), n_axis, map.data());
 }
 
-// The SNV tail both entry points share.  reserve_last_rows: every scratch array of n_snv rows and room for as many new rows behind the
-// sample's (a call adds at most one row per SNV row) -- before anything is launched.  launch_last_rows: st->keys_in / idx_in hold the
-// (set position, mm) keys of the source rows; sort, flag the last row of every position, scan, gather them behind the sample's rows.
-int reserve_last_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv)
+// one of a sample's two row tables -- compare rows (CsRow), pool rows (PoolRow) -- as the SNV tail and the re-sort see it
+template <class Row>
+struct RowTable { Row *&rows; size_t &n, &cap; bool &sorted; };
+
+RowTable<CsRow> own_rows(Sample &sm) { return {sm.rows, sm.n_rows, sm.cap_rows, sm.sorted}; }
+RowTable<PoolRow> pool_rows(Sample &sm) { return {sm.prows, sm.n_prows, sm.cap_prows, sm.psorted}; }
+
+// room for n_snv new rows behind the table's (a call adds at most one row per SNV row)
+template <class Row>
+int reserve_rows(isx_cmpset *st, RowTable<Row> t, uint32_t n_snv)
 {
+    hipStream_t s = st->ctx->stream;
+    if (t.cap >= t.n + n_snv) return ISX_OK;
+    const size_t want = std::max(t.n + n_snv, t.cap * 2);
+    Row *grown = nullptr;
+    HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(Row)));
+    if (t.n) HIP_TRY(hipMemcpyAsync(grown, t.rows, t.n * sizeof(Row), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(isx_wait_stream(s));
+    if (t.rows) isx_dev_free(t.rows);
+    t.rows = grown; t.cap = want;
+    return ISX_OK;
+}
+
+// The SNV tail both entry points share.  reserve_snv_tail: every scratch array of n_snv rows -- one set, which the pool rows' pass
+// uses after the compare rows' -- and room in the sample's table(s), all before anything is launched.
+int reserve_snv_tail(isx_cmpset *st, Sample &sm, uint32_t n_snv, bool pool)
+{
+    if (!n_snv) return ISX_OK;
     hipStream_t s = st->ctx->stream;
     HIP_TRY(st->keys.fit(n_snv)); HIP_TRY(st->keys_in.fit(n_snv)); HIP_TRY(st->idx.fit(n_snv)); HIP_TRY(st->idx_in.fit(n_snv));
     HIP_TRY(st->flags.fit(n_snv)); HIP_TRY(st->pos.fit((size_t)n_snv + 1));
     size_t t_sort = 0, t_scan = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
     HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
-    const int rc = grow_temp(st, std::max(t_sort, t_scan));
-    if (rc) return rc;
-    if (sm.cap_rows < sm.n_rows + n_snv) {
-        const size_t want = std::max(sm.n_rows + n_snv, sm.cap_rows * 2);
-        CsRow *grown = nullptr;
-        HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(CsRow)));
-        if (sm.n_rows) HIP_TRY(hipMemcpyAsync(grown, sm.rows, sm.n_rows * sizeof(CsRow), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(isx_wait_stream(s));
-        if (sm.rows) isx_dev_free(sm.rows);
-        sm.rows = grown; sm.cap_rows = want;
-    }
-    return ISX_OK;
+    int rc = grow_temp(st, std::max(t_sort, t_scan));
+    if (!rc) rc = reserve_rows(st, own_rows(sm), n_snv);
+    if (!rc && pool) rc = reserve_rows(st, pool_rows(sm), n_snv);
+    return rc;
 }
 
-template <class Src>
-int launch_last_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv, const Src *d_snv, uint32_t *n_new)
+// launch_rows: st->keys_in / idx_in hold the (set position, mm) keys of the source rows (the pooling keys for the pool rows); sort,
+// flag the last row of every position, scan, gather them behind the table's rows; *n_new = how many, once the stream has drained
+template <class Src, class Row>
+int launch_rows(isx_cmpset *st, RowTable<Row> t, uint32_t n_snv, const Src *d_snv, const uint8_t *d_snv_flags, uint32_t *n_new)
 {
     hipStream_t s = st->ctx->stream;
     const dim3 blk(256), grid((n_snv + 255) / 256);
@@ -442,57 +410,32 @@ int launch_last_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv, const Src *d_sn
     hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
     tb = st->temp.cap;
     HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL(k_gather_last<Src>, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, d_snv,
-                       sm.rows + sm.n_rows, (uint32_t)(sm.cap_rows - sm.n_rows), st->pos.p + n_snv);
+    hipLaunchKernelGGL((k_gather_last<Src, Row>), grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, d_snv, d_snv_flags,
+                       t.rows + t.n, (uint32_t)(t.cap - t.n), st->pos.p + n_snv);
     HIP_TRY(hipMemcpyAsync(n_new, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
     return ISX_OK;
 }
 
-// The same tail for the pool rows (after reserve_last_rows, whose scratch it shares): room behind the sample's pool rows, then -- the
-// pooling keys in st->keys_in / idx_in -- sort, flag, scan, gather into PoolRow.
-int reserve_pool_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv)
+// the call's n_new rows are the table's; out_of_order: the call brought a scaffold below one the sample already had
+template <class Row>
+void commit_rows(RowTable<Row> t, uint32_t n_new, bool out_of_order)
 {
-    hipStream_t s = st->ctx->stream;
-    if (sm.cap_prows < sm.n_prows + n_snv) {
-        const size_t want = std::max(sm.n_prows + n_snv, sm.cap_prows * 2);
-        PoolRow *grown = nullptr;
-        HIP_TRY(isx_raw_dev_malloc(&grown, want * sizeof(PoolRow)));
-        if (sm.n_prows) HIP_TRY(hipMemcpyAsync(grown, sm.prows, sm.n_prows * sizeof(PoolRow), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(isx_wait_stream(s));
-        if (sm.prows) isx_dev_free(sm.prows);
-        sm.prows = grown; sm.cap_prows = want;
-    }
-    return ISX_OK;
-}
-
-template <class Src>
-int launch_pool_rows(isx_cmpset *st, Sample &sm, uint32_t n_snv, const Src *d_snv, const uint8_t *d_snv_flags, uint32_t *n_new)
-{
-    hipStream_t s = st->ctx->stream;
-    const dim3 blk(256), grid((n_snv + 255) / 256);
-    size_t tb = st->temp.cap;
-    HIP_TRY(rocprim::radix_sort_pairs(st->temp.p, tb, st->keys_in.p, st->keys.p, st->idx_in.p, st->idx.p, n_snv, 0, 64, s));
-    hipLaunchKernelGGL(k_last_flags, grid, blk, 0, s, st->keys.p, n_snv, st->flags.p);
-    tb = st->temp.cap;
-    HIP_TRY(rocprim::exclusive_scan(st->temp.p, tb, st->flags.p, st->pos.p, 0u, n_snv, rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL(k_gather_pool<Src>, grid, blk, 0, s, st->keys.p, st->idx.p, st->flags.p, st->pos.p, n_snv, d_snv, d_snv_flags,
-                       sm.prows + sm.n_prows, (uint32_t)(sm.cap_prows - sm.n_prows), st->pos.p + n_snv);
-    HIP_TRY(hipMemcpyAsync(n_new, st->pos.p + n_snv, 4, hipMemcpyDeviceToHost, s));
-    return ISX_OK;
+    if (n_new && t.n && out_of_order) t.sorted = false;
+    t.n += std::min<size_t>(n_new, t.cap - t.n);
 }
 
 // rows (compare rows or pool rows) of a sample whose batches did not arrive in set order: one sort by position
 template <class Row>
-int sort_rows_of(isx_cmpset *st, Row *&rows, size_t n_rows, size_t cap_rows, bool &sorted)
+int sort_rows_of(isx_cmpset *st, RowTable<Row> t)
 {
-    if (sorted || n_rows < 2) { sorted = true; return ISX_OK; }
+    if (t.sorted || t.n < 2) { t.sorted = true; return ISX_OK; }
     hipStream_t s = st->ctx->stream;
-    const uint32_t n = (uint32_t)n_rows;
+    const uint32_t n = (uint32_t)t.n;
     SetBuf<uint32_t> k_in, k_out;
     Row *fresh = nullptr;
     auto done = [&](int rc) { k_in.drop(); k_out.drop(); if (fresh) isx_dev_free(fresh); return rc; };
     if (k_in.fit(n) != hipSuccess || k_out.fit(n) != hipSuccess || st->idx_in.fit(n) != hipSuccess || st->idx.fit(n) != hipSuccess ||
-        isx_raw_dev_malloc(&fresh, cap_rows * sizeof(Row)) != hipSuccess) {
+        isx_raw_dev_malloc(&fresh, t.cap * sizeof(Row)) != hipSuccess) {
         isx_set_error("isx_cmpset_compare: out of device memory while ordering a sample's SNV rows");
         return done(ISX_ERR_HIP);
     }
@@ -501,28 +444,123 @@ int sort_rows_of(isx_cmpset *st, Row *&rows, size_t n_rows, size_t cap_rows, boo
     int rc = grow_temp(st, tb);
     if (rc) return done(rc);
     const dim3 blk(256), grid((n + 255) / 256);
-    hipLaunchKernelGGL(k_row_keys<Row>, grid, blk, 0, s, rows, n, k_in.p, st->idx_in.p);
+    hipLaunchKernelGGL(k_row_keys<Row>, grid, blk, 0, s, t.rows, n, k_in.p, st->idx_in.p);
     tb = st->temp.cap;
     if (rocprim::radix_sort_pairs(st->temp.p, tb, k_in.p, k_out.p, st->idx_in.p, st->idx.p, n, 0, 32, s) != hipSuccess) {
         isx_set_error("isx_cmpset_compare: radix sort of a sample's SNV rows failed");
         return done(ISX_ERR_HIP);
     }
-    hipLaunchKernelGGL(k_gather_rows<Row>, grid, blk, 0, s, rows, st->idx.p, n, fresh);
+    hipLaunchKernelGGL(k_gather_rows<Row>, grid, blk, 0, s, t.rows, st->idx.p, n, fresh);
     if (isx_wait_stream(s) != hipSuccess) { isx_set_error("isx_cmpset_compare: ordering a sample's SNV rows failed"); return done(ISX_ERR_HIP); }
-    std::swap(rows, fresh);
-    sorted = true;
+    std::swap(t.rows, fresh);
+    t.sorted = true;
     return done(ISX_OK);
 }
 
-int sort_rows(isx_cmpset *st, Sample &sm) { return sort_rows_of(st, sm.rows, sm.n_rows, sm.cap_rows, sm.sorted); }
+int sort_rows(isx_cmpset *st, Sample &sm) { return sort_rows_of(st, own_rows(sm)); }
 
 int pow2_ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+// ---- what isx_cmpset_add and the stored-profile entry points do alike around their own passes ----
+struct Caller {
+    std::string who;                    // heads every error text: "isx_cmpset_add: "
+    const char *unit, *units;           // what the entry point's texts call one call and several: "batch" / "batches"
+};
+
+// the call's level values ascend strictly within 0..65535 and are those of the sample's earlier calls; *fresh: it has had none
+int check_levels(const Caller &c, const isx_cmpset *st, int32_t sample, const std::vector<int32_t> &mmv, bool *fresh)
+{
+    for (size_t k = 0; k < mmv.size(); k++)
+        if (mmv[k] < 0 || mmv[k] > 65535 || (k && mmv[k] <= mmv[k - 1])) {
+            isx_set_error(c.who + "level_mm_values must ascend strictly within 0..65535");
+            return ISX_ERR_ARG;
+        }
+    *fresh = (size_t)sample >= st->samples.size() || st->samples[(size_t)sample].mm.empty();
+    if (!*fresh && st->samples[(size_t)sample].mm != mmv) {
+        isx_set_error(c.who + "this " + c.unit + "'s level_mm_values differ from those of the sample's earlier " + c.units);
+        return ISX_ERR_ARG;
+    }
+    return ISX_OK;
+}
+
+struct Claim {
+    std::vector<int64_t> set_pos0;      // per scaffold of the call: its first set position, -1 when the set does not name it
+    std::vector<int32_t> named;         // the call's scaffolds the set names
+    int32_t min_sid, max_sid;           // the lowest and highest set scaffold among them
+};
+
+// the call's scaffolds, ids[i] = scaffold of the set or -1: each within the set, of the set's length where the call has lengths of its
+// own (bounds: n + 1 ascending bounds, or NULL), and new to the sample
+int claim_scaffolds(const Caller &c, const isx_cmpset *st, int32_t sample, bool fresh, int32_t n, const int32_t *ids, const int64_t *bounds,
+                    Claim &out)
+{
+    std::vector<uint8_t> seen((size_t)st->n_scaf, 0);
+    out.set_pos0.assign((size_t)n, -1);
+    out.named.clear();
+    out.min_sid = st->n_scaf; out.max_sid = -1;
+    for (int i = 0; i < n; i++) {
+        const int32_t sid = ids[i];
+        if (sid == -1) continue;
+        if (sid < 0 || sid >= st->n_scaf) { isx_set_error(c.who + "set_scaffold_ids[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
+        if (bounds && bounds[i + 1] - bounds[i] != st->len[(size_t)sid]) {
+            isx_set_error(c.who + "batch scaffold " + std::to_string(i) + " has not the length of set scaffold " + std::to_string(sid));
+            return ISX_ERR_ARG;
+        }
+        if (seen[(size_t)sid] || (!fresh && st->samples[(size_t)sample].have[(size_t)sid])) {
+            isx_set_error(c.who + "scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was added before");
+            return ISX_ERR_STATE;
+        }
+        seen[(size_t)sid] = 1;
+        out.set_pos0[(size_t)i] = st->spos[(size_t)sid];
+        out.named.push_back(i);
+        out.min_sid = std::min(out.min_sid, sid); out.max_sid = std::max(out.max_sid, sid);
+    }
+    return ISX_OK;
+}
+
+// the sample's slot; its first call fixes its levels and gives it zeroed planes.  Whatever was derived from the set as it was -- the
+// pair counters, the clustering, the sites, ranks and pulled counts of isx_cmpset_pool_sites -- no longer holds.
+int open_sample(isx_cmpset *st, int32_t sample, int n_levels, Sample **out)
+{
+    if ((size_t)sample >= st->samples.size()) st->samples.resize((size_t)sample + 1);
+    Sample &sm = st->samples[(size_t)sample];
+    if (sm.mm.empty()) {
+        if (sm.planes) isx_dev_free(sm.planes);
+        sm.planes = nullptr;
+        HIP_TRY(isx_raw_dev_malloc(&sm.planes, (size_t)n_levels * (size_t)st->n_words * 8));
+        HIP_TRY(hipMemsetAsync(sm.planes, 0, (size_t)n_levels * (size_t)st->n_words * 8, st->ctx->stream));
+        sm.have.assign((size_t)st->n_scaf, 0);
+        sm.present.assign((size_t)st->n_scaf * n_levels, 0);
+    }
+    st->compared = false;
+    st->clustered = false;
+    st->pooled = false;
+    *out = &sm;
+    return ISX_OK;
+}
+
+// only now is the call part of the sample.  present_at(i, k): level k is a key of the covT of the call's scaffold i
+template <class PresentAt>
+void commit_call(Sample &sm, const std::vector<int32_t> &mmv, const int32_t *ids, const Claim &cl, PresentAt present_at, uint32_t n_new,
+                 uint32_t n_new_pool)
+{
+    const size_t L = mmv.size();
+    if (sm.mm.empty()) sm.mm = mmv;
+    for (const int32_t i : cl.named) {
+        sm.have[(size_t)ids[i]] = 1;
+        for (size_t k = 0; k < L; k++) sm.present[(size_t)ids[i] * L + k] = present_at(i, (int)k) ? 1 : 0;
+    }
+    const bool out_of_order = cl.min_sid < sm.max_sid;
+    commit_rows(own_rows(sm), n_new, out_of_order);
+    commit_rows(pool_rows(sm), n_new_pool, out_of_order);
+    sm.max_sid = std::max(sm.max_sid, cl.max_sid);
+}
 
 }  // namespace
 
 namespace isxset {
 
-int cmpset_sort_pool_rows(isx_cmpset *st, Sample &sm) { return sort_rows_of(st, sm.prows, sm.n_prows, sm.cap_prows, sm.psorted); }
+int cmpset_sort_pool_rows(isx_cmpset *st, Sample &sm) { return sort_rows_of(st, pool_rows(sm)); }
 
 int cmpset_check_batch(const char *who, const isx_cmpset *st, int32_t sample, const isx_batch *b, int32_t n_bscaf, const int64_t *bb,
                        const int32_t *ids)
@@ -603,77 +641,39 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
         isx_set_error("isx_cmpset_add: a batch of " + std::to_string(M) + " levels; a set compares at most " + std::to_string(ISX_CMPSET_MAX_LEVELS));
         return ISX_ERR_CAPACITY;
     }
+    const Caller who{"isx_cmpset_add: ", "batch", "batches"};
     std::vector<int32_t> mmv((size_t)M);
-    for (int k = 0; k < M; k++) {
-        mmv[(size_t)k] = level_mm_values ? level_mm_values[k] : k;
-        if (mmv[(size_t)k] < 0 || mmv[(size_t)k] > 65535 || (k && mmv[(size_t)k] <= mmv[(size_t)k - 1])) {
-            isx_set_error("isx_cmpset_add: level_mm_values must ascend strictly within 0..65535");
-            return ISX_ERR_ARG;
-        }
-    }
-    const bool fresh = (size_t)sample >= st->samples.size() || st->samples[(size_t)sample].mm.empty();
-    if (!fresh && st->samples[(size_t)sample].mm != mmv) {
-        isx_set_error("isx_cmpset_add: this batch's level_mm_values differ from those of the sample's earlier batches");
-        return ISX_ERR_ARG;
-    }
-    std::vector<uint8_t> seen((size_t)st->n_scaf, 0);
+    for (int k = 0; k < M; k++) mmv[(size_t)k] = level_mm_values ? level_mm_values[k] : k;
+    bool fresh = false;
+    Claim cl;
+    int rc = check_levels(who, st, sample, mmv, &fresh);
+    if (!rc) rc = claim_scaffolds(who, st, sample, fresh, n_bscaf, ids, bb, cl);
+    if (rc) return rc;
+    if (cl.named.empty()) return ISX_OK;            // nothing of this batch is in the set
     std::vector<PackJob> jobs;
-    std::vector<int64_t> set_pos0((size_t)n_bscaf, -1);
     int64_t jw = 0;
-    int32_t min_sid = st->n_scaf, max_sid = -1;
-    for (int i = 0; i < n_bscaf; i++) {
-        const int32_t sid = ids[i];
-        if (sid == -1) continue;
-        if (sid < 0 || sid >= st->n_scaf) { isx_set_error("isx_cmpset_add: set_scaffold_ids[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
-        if (bb[i + 1] - bb[i] != st->len[(size_t)sid]) {
-            isx_set_error("isx_cmpset_add: batch scaffold " + std::to_string(i) + " has not the length of set scaffold " + std::to_string(sid));
-            return ISX_ERR_ARG;
-        }
-        if (seen[(size_t)sid] || (!fresh && st->samples[(size_t)sample].have[(size_t)sid])) {
-            isx_set_error("isx_cmpset_add: scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was added before");
-            return ISX_ERR_STATE;
-        }
-        seen[(size_t)sid] = 1;
-        jobs.push_back({jw, st->woff[(size_t)sid], bb[i], st->len[(size_t)sid]});
-        jw += st->woff[(size_t)sid + 1] - st->woff[(size_t)sid];
-        set_pos0[(size_t)i] = st->spos[(size_t)sid];
-        min_sid = std::min(min_sid, sid); max_sid = std::max(max_sid, sid);
+    for (const int32_t i : cl.named) {
+        const size_t sid = (size_t)ids[i];
+        jobs.push_back({jw, st->woff[sid], bb[i], st->len[sid]});
+        jw += st->woff[sid + 1] - st->woff[sid];
     }
-    if (jobs.empty()) return ISX_OK;                // nothing of this batch is in the set
     const int n_jobs = (int)jobs.size();
     jobs.push_back({jw, 0, 0, 0});
     const uint32_t n_snv = (uint32_t)b->sizes.n_snv, n_pos = (uint32_t)b->n_pos;
 
     HIP_TRY(hipSetDevice(st->ctx->device));
     hipStream_t s = st->ctx->stream;
-    if ((size_t)sample >= st->samples.size()) st->samples.resize((size_t)sample + 1);
-    Sample &sm = st->samples[(size_t)sample];
-    if (sm.mm.empty()) {                            // the sample's first batch fixes its levels
-        if (sm.planes) isx_dev_free(sm.planes);
-        sm.planes = nullptr;
-        HIP_TRY(isx_raw_dev_malloc(&sm.planes, (size_t)M * (size_t)st->n_words * 8));
-        HIP_TRY(hipMemsetAsync(sm.planes, 0, (size_t)M * (size_t)st->n_words * 8, s));
-        sm.have.assign((size_t)st->n_scaf, 0);
-        sm.present.assign((size_t)st->n_scaf * M, 0);
-    }
-    st->compared = false;
-    st->clustered = false;
-    st->pooled = false;                             // the sites, ranks and pulled counts of isx_cmpset_pool_sites are of the set as it was
+    Sample *opened = nullptr;
+    if ((rc = open_sample(st, sample, M, &opened))) return rc;
+    Sample &sm = *opened;
     // scratch, all sized before anything is launched
     HIP_TRY(st->cov.fit(n_pos)); HIP_TRY(st->scratch_f.fit((size_t)n_pos * 2));
     HIP_TRY(st->acc.fit(level_acc_bytes(n_bscaf))); HIP_TRY(st->present.fit((size_t)n_bscaf * M));
     const std::vector<int64_t> h_bounds(bb, bb + n_bscaf + 1);
     HIP_TRY(st->bbounds.put(h_bounds, s));
-    HIP_TRY(st->set_pos0.put(set_pos0, s));
+    HIP_TRY(st->set_pos0.put(cl.set_pos0, s));
     HIP_TRY(st->jobs.put(jobs, s));
-    if (n_snv) {
-        const int rc = reserve_last_rows(st, sm, n_snv);
-        if (rc) return rc;
-        if (st->pool_on) {
-            const int rcp = reserve_pool_rows(st, sm, n_snv);
-            if (rcp) return rcp;
-        }
-    }
+    if ((rc = reserve_snv_tail(st, sm, n_snv, st->pool_on))) return rc;
     SummaryIn in{};
     fill_summary_in(b, n_bscaf, bb, in);
     in.stream = s;
@@ -692,32 +692,19 @@ int isx_cmpset_add(isx_cmpset *st, int32_t sample, isx_batch *b, int32_t n_bscaf
     uint32_t n_new = 0;
     if (n_snv) {
         const dim3 grid((n_snv + 255) / 256);
-        hipLaunchKernelGGL(k_set_keys, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
-        const int rc = launch_last_rows(st, sm, n_snv, b->d_snv, &n_new);
-        if (rc) return rc;
+        hipLaunchKernelGGL(k_set_keys<false>, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
+        if ((rc = launch_rows(st, own_rows(sm), n_snv, b->d_snv, (const uint8_t *)nullptr, &n_new))) return rc;
     }
     // pool rows: the same scheme on keys that leave the cryptic rows out, so a position's last row is its highest-mm row that counts
     uint32_t n_new_pool = 0;
     if (n_snv && st->pool_on) {
         const dim3 grid((n_snv + 255) / 256);
-        hipLaunchKernelGGL(k_pool_keys, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
-        const int rc = launch_pool_rows(st, sm, n_snv, b->d_snv, (const uint8_t *)nullptr, &n_new_pool);
-        if (rc) return rc;
+        hipLaunchKernelGGL(k_set_keys<true>, grid, blk, 0, s, b->d_snv, n_snv, st->bbounds.p, n_bscaf, st->set_pos0.p, st->keys_in.p, st->idx_in.p);
+        if ((rc = launch_rows(st, pool_rows(sm), n_snv, b->d_snv, (const uint8_t *)nullptr, &n_new_pool))) return rc;
     }
     HIP_TRY(isx_wait_stream(s));
     HIP_TRY(hipGetLastError());
-    // only now is the batch part of the sample
-    if (sm.mm.empty()) sm.mm = mmv;
-    for (int i = 0; i < n_bscaf; i++) {
-        if (ids[i] < 0) continue;
-        sm.have[(size_t)ids[i]] = 1;
-        for (int mm = 0; mm < M; mm++) sm.present[(size_t)ids[i] * M + mm] = present[(size_t)mm * n_bscaf + i] ? 1 : 0;
-    }
-    if (n_new && sm.n_rows && min_sid < sm.max_sid) sm.sorted = false;
-    sm.n_rows += std::min<size_t>(n_new, sm.cap_rows - sm.n_rows);
-    if (n_new_pool && sm.n_prows && min_sid < sm.max_sid) sm.psorted = false;
-    sm.n_prows += std::min<size_t>(n_new_pool, sm.cap_prows - sm.n_prows);
-    sm.max_sid = std::max(sm.max_sid, max_sid);
+    commit_call(sm, mmv, ids, cl, [&](int i, int mm) { return present[(size_t)mm * n_bscaf + i] != 0; }, n_new, n_new_pool);
     return ISX_OK;
 }
 
@@ -726,7 +713,8 @@ static int add_profile(bool pool, isx_cmpset *st, int32_t sample, int32_t n_csca
                        const uint8_t *present, const int64_t *off, const uint32_t *positions, const uint32_t *values, int64_t n_snv_in,
                        const isx_profile_snv *snv, const uint8_t *snv_flags, float *device_ms)
 {
-    const std::string who(pool ? "isx_cmpset_add_profile_pool: " : "isx_cmpset_add_profile: ");
+    const Caller caller{pool ? "isx_cmpset_add_profile_pool: " : "isx_cmpset_add_profile: ", "call", "calls"};
+    const std::string &who = caller.who;
     if (device_ms) *device_ms = 0.f;
     if (!st || sample < 0 || sample >= ISX_CMPSET_MAX_SAMPLES || n_cscaf <= 0 || !ids || L <= 0 || !level_mm_values || !present || !off ||
         n_snv_in < 0 || (n_snv_in && (!snv || (pool && !snv_flags)))) {
@@ -747,35 +735,14 @@ static int add_profile(bool pool, isx_cmpset *st, int32_t sample, int32_t n_csca
     }
     if (n_snv_in > (int64_t)0x7FFFFFFFll) { isx_set_error(who + "more SNV rows than one call holds"); return ISX_ERR_CAPACITY; }
     const std::vector<int32_t> mmv(level_mm_values, level_mm_values + L);
-    for (int k = 0; k < L; k++)
-        if (mmv[(size_t)k] < 0 || mmv[(size_t)k] > 65535 || (k && mmv[(size_t)k] <= mmv[(size_t)k - 1])) {
-            isx_set_error(who + "level_mm_values must ascend strictly within 0..65535");
-            return ISX_ERR_ARG;
-        }
-    const bool fresh = (size_t)sample >= st->samples.size() || st->samples[(size_t)sample].mm.empty();
-    if (!fresh && st->samples[(size_t)sample].mm != mmv) {
-        isx_set_error(who + "this call's level_mm_values differ from those of the sample's earlier calls");
-        return ISX_ERR_ARG;
-    }
-    // the call's scaffolds
-    std::vector<uint8_t> seen((size_t)st->n_scaf, 0);
-    std::vector<int64_t> set_pos0((size_t)n_cscaf, -1), sub_len;
-    std::vector<int32_t> sub_scaf;                  // the call's scaffolds the set names
-    int32_t min_sid = st->n_scaf, max_sid = -1;
-    for (int i = 0; i < n_cscaf; i++) {
-        const int32_t sid = ids[i];
-        if (sid == -1) continue;
-        if (sid < 0 || sid >= st->n_scaf) { isx_set_error(who + "set_scaffold_ids[" + std::to_string(i) + "] outside the set"); return ISX_ERR_ARG; }
-        if (seen[(size_t)sid] || (!fresh && st->samples[(size_t)sample].have[(size_t)sid])) {
-            isx_set_error(who + "scaffold " + std::to_string(sid) + " of sample " + std::to_string(sample) + " was added before");
-            return ISX_ERR_STATE;
-        }
-        seen[(size_t)sid] = 1;
-        set_pos0[(size_t)i] = st->spos[(size_t)sid];
-        sub_scaf.push_back(i);
-        sub_len.push_back(st->len[(size_t)sid]);
-        min_sid = std::min(min_sid, sid); max_sid = std::max(max_sid, sid);
-    }
+    bool fresh = false;
+    Claim cl;
+    int rc = check_levels(caller, st, sample, mmv, &fresh);
+    if (!rc) rc = claim_scaffolds(caller, st, sample, fresh, n_cscaf, ids, nullptr, cl);
+    if (rc) return rc;
+    const std::vector<int32_t> &sub_scaf = cl.named;
+    std::vector<int64_t> sub_len;
+    for (const int32_t i : sub_scaf) sub_len.push_back(st->len[(size_t)ids[i]]);
     // the covT series
     const int64_t n_series = (int64_t)n_cscaf * L;
     if (off[0] != 0) { isx_set_error(who + "entry_offsets must start at 0"); return ISX_ERR_ARG; }
@@ -833,28 +800,14 @@ static int add_profile(bool pool, isx_cmpset *st, int32_t sample, int32_t n_csca
 
     HIP_TRY(hipSetDevice(st->ctx->device));
     hipStream_t s = st->ctx->stream;
-    if ((size_t)sample >= st->samples.size()) st->samples.resize((size_t)sample + 1);
-    Sample &sm = st->samples[(size_t)sample];
-    if (sm.mm.empty()) {                            // the sample's first call fixes its levels
-        if (sm.planes) isx_dev_free(sm.planes);
-        sm.planes = nullptr;
-        HIP_TRY(isx_raw_dev_malloc(&sm.planes, (size_t)L * (size_t)st->n_words * 8));
-        HIP_TRY(hipMemsetAsync(sm.planes, 0, (size_t)L * (size_t)st->n_words * 8, s));
-        sm.have.assign((size_t)st->n_scaf, 0);
-        sm.present.assign((size_t)st->n_scaf * L, 0);
-    }
-    st->compared = false;
-    st->clustered = false;
-    st->pooled = false;
+    Sample *opened = nullptr;
+    if ((rc = open_sample(st, sample, L, &opened))) return rc;
+    Sample &sm = *opened;
     // scratch and uploads, all sized before anything is launched
     HIP_TRY(st->pf_off.fit((size_t)n_series + 1)); HIP_TRY(st->pf_pos.fit((size_t)n_entries)); HIP_TRY(st->pf_val.fit((size_t)n_entries));
     HIP_TRY(st->pf_snv.fit(n_snv));
     if (pool) HIP_TRY(st->pf_flags.fit(n_snv));
-    if (n_snv) {
-        int rc = reserve_last_rows(st, sm, n_snv);
-        if (!rc && pool) rc = reserve_pool_rows(st, sm, n_snv);
-        if (rc) return rc;
-    }
+    if ((rc = reserve_snv_tail(st, sm, n_snv, pool))) return rc;
     HIP_TRY(hipMemcpyAsync(st->pf_off.p, off, ((size_t)n_series + 1) * 8, hipMemcpyHostToDevice, s));
     if (n_entries) {
         HIP_TRY(hipMemcpyAsync(st->pf_pos.p, positions, (size_t)n_entries * 4, hipMemcpyHostToDevice, s));
@@ -863,40 +816,27 @@ static int add_profile(bool pool, isx_cmpset *st, int32_t sample, int32_t n_csca
     if (n_snv) HIP_TRY(hipMemcpyAsync(st->pf_snv.p, snv, (size_t)n_snv * sizeof(isx_profile_snv), hipMemcpyHostToDevice, s));
     if (n_snv && pool) HIP_TRY(hipMemcpyAsync(st->pf_flags.p, snv_flags, n_snv, hipMemcpyHostToDevice, s));
     HIP_TRY(st->pf_tiles.put(tiles, s));
-    HIP_TRY(st->set_pos0.put(set_pos0, s));
+    HIP_TRY(st->set_pos0.put(cl.set_pos0, s));
     HIP_TRY(hipEventRecord(st->ev[0], s));
     hipLaunchKernelGGL(k_profile_planes, dim3((unsigned)n_tiles), dim3(256), 0, s, st->pf_tiles.p, st->pf_off.p, (int)L, st->pf_pos.p,
                        st->pf_val.p, (uint32_t)st->min_cov, sm.planes, st->n_words);
     uint32_t n_new = 0;
     if (n_snv) {
-        hipLaunchKernelGGL(k_profile_keys, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, n_snv, st->set_pos0.p, (int)n_cscaf,
-                           st->keys_in.p, st->idx_in.p);
-        const int rc = launch_last_rows(st, sm, n_snv, st->pf_snv.p, &n_new);
-        if (rc) return rc;
+        hipLaunchKernelGGL(k_profile_keys<false>, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, (const uint8_t *)nullptr, n_snv,
+                           st->set_pos0.p, (int)n_cscaf, st->keys_in.p, st->idx_in.p);
+        if ((rc = launch_rows(st, own_rows(sm), n_snv, st->pf_snv.p, (const uint8_t *)nullptr, &n_new))) return rc;
     }
     uint32_t n_new_pool = 0;                        // pool rows: as isx_cmpset_add makes them, the cryptic rows keyed out
     if (n_snv && pool) {
-        hipLaunchKernelGGL(k_profile_pool_keys, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, st->pf_flags.p, n_snv, st->set_pos0.p,
-                           (int)n_cscaf, st->keys_in.p, st->idx_in.p);
-        const int rc = launch_pool_rows(st, sm, n_snv, st->pf_snv.p, st->pf_flags.p, &n_new_pool);
-        if (rc) return rc;
+        hipLaunchKernelGGL(k_profile_keys<true>, dim3((n_snv + 255) / 256), dim3(256), 0, s, st->pf_snv.p, st->pf_flags.p, n_snv,
+                           st->set_pos0.p, (int)n_cscaf, st->keys_in.p, st->idx_in.p);
+        if ((rc = launch_rows(st, pool_rows(sm), n_snv, st->pf_snv.p, st->pf_flags.p, &n_new_pool))) return rc;
     }
     HIP_TRY(hipEventRecord(st->ev[1], s));
     HIP_TRY(isx_wait_stream(s));
     HIP_TRY(hipGetLastError());
     if (device_ms) (void)hipEventElapsedTime(device_ms, st->ev[0], st->ev[1]);
-    // only now is the call part of the sample
-    if (sm.mm.empty()) sm.mm = mmv;
-    for (int i = 0; i < n_cscaf; i++) {
-        if (ids[i] < 0) continue;
-        sm.have[(size_t)ids[i]] = 1;
-        for (int k = 0; k < L; k++) sm.present[(size_t)ids[i] * L + k] = present[(size_t)i * L + k] ? 1 : 0;
-    }
-    if (n_new && sm.n_rows && min_sid < sm.max_sid) sm.sorted = false;
-    sm.n_rows += std::min<size_t>(n_new, sm.cap_rows - sm.n_rows);
-    if (n_new_pool && sm.n_prows && min_sid < sm.max_sid) sm.psorted = false;
-    sm.n_prows += std::min<size_t>(n_new_pool, sm.cap_prows - sm.n_prows);
-    sm.max_sid = std::max(sm.max_sid, max_sid);
+    commit_call(sm, mmv, ids, cl, [&](int i, int k) { return present[(size_t)i * L + k] != 0; }, n_new, n_new_pool);
     return ISX_OK;
 }
 
@@ -1039,7 +979,7 @@ int isx_cmpset_compare(isx_cmpset *st, double min_freq, int64_t cap_rows, isx_co
     }
     SnpArgs sa{};
     sa.rows = st->d_rows.p; sa.n_rows = st->d_n_rows.p; sa.pairs = d_pairs.p; sa.cand_off = d_cand.p; sa.n_pairs = (int)pairs.size();
-    sa.lut = st->ctx->d_lut; sa.lut_n = st->ctx->lut_n; sa.fallback = st->ctx->fallback; sa.min_freq = min_freq;
+    sa.nm = {st->ctx->d_lut, st->ctx->lut_n, st->ctx->fallback, min_freq};
     sa.planes = st->d_planes.p; sa.lmap = st->d_lmap.p; sa.A = A; sa.n_words = st->n_words; sa.spos = st->d_spos.p; sa.n_scaf = n_scaf;
     sa.pres = st->d_pres.p; sa.n_con = st->d_snp.p; sa.n_pop = st->d_snp.p + n_snp; sa.failed = st->d_failed.p; sa.n_out = (uint32_t)n_pairs;
     sa.axis_mm = st->d_axis.p; sa.out_rows = nullptr; sa.cursor = st->d_cursor.p; sa.cap_rows = 0;
@@ -1112,7 +1052,7 @@ int isx_cmpset_pair_snps(isx_cmpset *st, int32_t i, int32_t j, int64_t *n_rows)
     PS_TRY(hipMemsetAsync(st->d_cursor.p, 0, 4, s));
     SnpArgs sa{};
     sa.rows = st->d_rows.p; sa.n_rows = st->d_n_rows.p; sa.pairs = d_pair.p; sa.cand_off = d_cand.p; sa.n_pairs = 1;
-    sa.lut = st->ctx->d_lut; sa.lut_n = st->ctx->lut_n; sa.fallback = st->ctx->fallback; sa.min_freq = st->min_freq;
+    sa.nm = {st->ctx->d_lut, st->ctx->lut_n, st->ctx->fallback, st->min_freq};
     sa.planes = st->d_planes.p; sa.lmap = st->d_lmap.p; sa.A = A; sa.n_words = st->n_words; sa.spos = st->d_spos.p; sa.n_scaf = n_scaf;
     sa.pres = st->d_pres.p; sa.n_con = d_cnt.p; sa.n_pop = d_cnt.p + (size_t)n_scaf * A; sa.failed = d_failed.p; sa.n_out = 1;
     sa.axis_mm = st->d_axis.p; sa.out_rows = st->snp_rows.p; sa.cursor = st->d_cursor.p; sa.cap_rows = (uint32_t)cap;

@@ -22,6 +22,7 @@
 
 #include "isx_internal.h"
 #include "isx_summary.h"
+#include "isx_snp_rules.h"
 
 namespace {
 
@@ -307,15 +308,6 @@ __device__ __forceinline__ int64_t last_row_of(const uint64_t *keys, uint32_t n,
     return (int64_t)lo - 1;
 }
 
-// readComparer.py:306-315 is_present
-__device__ __forceinline__ bool is_present(uint32_t count, uint32_t total, const uint8_t *lut, int32_t lut_n, int32_t fallback,
-                                           double min_freq)
-{
-    int32_t min_bases = fallback;
-    if (total < (uint32_t)lut_n && lut[total] != 255) min_bases = lut[total];
-    return (int64_t)count >= (int64_t)min_bases && ((double)count / (double)total) >= min_freq;
-}
-
 __global__ void __launch_bounds__(256) k_snp_candidates(const uint64_t *keys_a, const uint32_t *idx_a, uint32_t n_a, const isx_snv *snv_a,
                                                         const uint64_t *keys_b, const uint32_t *idx_b, uint32_t n_b, const isx_snv *snv_b,
                                                         const uint8_t *lut, int32_t lut_n, int32_t fallback, double min_freq,
@@ -332,33 +324,26 @@ __global__ void __launch_bounds__(256) k_snp_candidates(const uint64_t *keys_a, 
     if (!from_a && j >= 0) return;                                          // shared rows are judged from A's side
     SnpCand c;
     c.gpos = gpos;
-    bool con, pop;
+    const isxsnp::NullModel nm{lut, lut_n, fallback, min_freq};
+    uint32_t verdict;
     if (j < 0) {                            // the row exists in one sample only (the other's columns are NaN)
         const uint32_t r = (from_a ? idx_a : idx_b)[i];
         const isx_snv x = (from_a ? snv_a : snv_b)[r];
         c.row_a = from_a ? r : 0xFFFFFFFFu;
         c.row_b = from_a ? 0xFFFFFFFFu : r;
-        con = x.con_base != x.ref_base;                                     // call_con_snps :296-301
-        if (x.ref_base > 3) {               // '{ref_base}_2' with ref_base N: the reference raises KeyError
+        verdict = isxsnp::snp_verdict(x, (const isx_snv *)nullptr, nm);
+        if (verdict == isxsnp::SNP_REF_FAILS) {
             atomicOr(&cursors[2 + find_seg(bounds, n_seg, gpos)], 1u);
             return;
         }
-        const uint32_t total = x.cnt[0] + x.cnt[1] + x.cnt[2] + x.cnt[3];
-        pop = !is_present(x.cnt[x.ref_base], total, lut, lut_n, fallback, min_freq);   // call_pop_snps :329-344
     } else {
         const uint32_t ra = idx_a[i], rb = idx_b[j];
         const isx_snv a = snv_a[ra], b = snv_b[rb];
         c.row_a = ra; c.row_b = rb;
-        con = a.con_base != b.con_base;                                     // :304
-        const uint32_t ta = a.cnt[0] + a.cnt[1] + a.cnt[2] + a.cnt[3], tb = b.cnt[0] + b.cnt[1] + b.cnt[2] + b.cnt[3];
-        if (!con) pop = false;                                                              // :325
-        else if (is_present(b.cnt[a.con_base & 3], tb, lut, lut_n, fallback, min_freq)) pop = false;   // :349-355
-        else if (is_present(a.cnt[b.con_base & 3], ta, lut, lut_n, fallback, min_freq)) pop = false;   // :358-361
-        else if (a.allele_count > 1 && b.allele_count > 1 && a.var_base == b.var_base) pop = false;   // :364-367
-        else pop = true;
+        verdict = isxsnp::snp_verdict(a, &b, nm);
     }
-    if (!con && !pop) return;                                               // "Only keep SNPs" :281
-    c.flags = (con ? 1u : 0u) | (pop ? 2u : 0u);
+    if (!verdict) return;                                                   // "Only keep SNPs" :281
+    c.flags = verdict;                                                      // (SNP_CON = 1, SNP_POP = 2)
     cand[atomicAdd(&cursors[0], 1u)] = c;
 }
 
@@ -378,16 +363,8 @@ __global__ void __launch_bounds__(256) k_snp_apply(const SnpCand *cand, uint32_t
     memset(&r, 0, sizeof(r));
     r.gpos = c.gpos; r.mm = (uint16_t)mm;
     r.consensus_snp = c.flags & 1u; r.population_snp = (c.flags >> 1) & 1u;
-    if (c.row_a != 0xFFFFFFFFu) {
-        const isx_snv a = snv_a[c.row_a];
-        r.has_a = 1; r.con_a = a.con_base; r.ref_a = a.ref_base; r.var_a = a.var_base;
-        for (int k = 0; k < 4; k++) r.cnt_a[k] = a.cnt[k];
-    }
-    if (c.row_b != 0xFFFFFFFFu) {
-        const isx_snv b = snv_b[c.row_b];
-        r.has_b = 1; r.con_b = b.con_base; r.ref_b = b.ref_base; r.var_b = b.var_base;
-        for (int k = 0; k < 4; k++) r.cnt_b[k] = b.cnt[k];
-    }
+    if (c.row_a != 0xFFFFFFFFu) isxsnp::snp_fill_side<false>(r, snv_a[c.row_a]);
+    if (c.row_b != 0xFFFFFFFFu) isxsnp::snp_fill_side<true>(r, snv_b[c.row_b]);
     rows[atomicAdd(&cursors[1], 1u)] = r;
 }
 

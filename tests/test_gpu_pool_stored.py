@@ -390,6 +390,73 @@ def test_pull_by_observations_equals_pull_by_batch(ctx):
     assert c[1].tobytes() == c[2].tobytes() == c[3].tobytes() and c[1].sum() > 12 * 600 and c[3].max() >= 3012
 
 
+# ---- 4b. hand-built stored rows: both row tables out of set order, a cryptic top row, every branch of the verdict ----
+def _stored_row(scaffold, position, mm, ref, con, var="A", allele_count=1, counts=None, cryptic=False):
+    cnt = dict(A=0, C=0, T=0, G=0)
+    cnt.update(counts or {con: 20})
+    return dict(scaffold=scaffold, position=position, mm=mm, ref_base=ref, con_base=con, var_base=var, allele_count=allele_count,
+                **{"class": "SNS", "cryptic": cryptic}, **cnt)
+
+
+def test_hand_built_rows_out_of_order_in_a_pooling_set(ctx):
+    """Two samples from stored tables in a set with pooling; `a` brings its last scaffold first, so its compare rows AND its pool rows
+    lie out of set order and both are sorted once.  p:10 of `a` has a cryptic row at mm 1 above a plain one at mm 0: the compare row is
+    the mm 1 row, the pool row the mm 0 row; p:50 has a cryptic row only: a compare row, no pool row, no site.  On `big` (two tiles, a
+    row on its last position) the two samples differ in consensus at four positions, one per branch of call_pop_snps: `b` shows a's
+    consensus (5 of 30 reads; the null model asks for 3), `a` shows b's (10 of 30), both are multi-allelic with one var_base, none of
+    these (the one population SNP); at position 0 they agree (no SNP).  `n` has a row at an N reference in `a` alone: the scaffold
+    fails.  Every expectation below is worked out by hand from readComparer.py:292-367 and polymorpher.py:53-70."""
+    from instrain_amd import compare
+    lut, _ = util.load_lut()
+    assert int(lut[30]) == 3 and int(lut[20]) == 2
+    names, lengths = ["p", "n", "big"], [100, 70, 4097]
+    full = lambda ln: (np.arange(ln), np.full(ln, 9))
+    a_cov = {"p": {0: full(100), 1: (np.array([0]), np.array([1]))}, "n": {0: full(70)}, "big": {0: full(4097)}}
+    b_cov = {n: {0: full(ln)} for n, ln in zip(names, lengths)}
+    a_rows = pd.DataFrame([
+        _stored_row("p", 10, 1, "A", "G", cryptic=True), _stored_row("p", 10, 0, "A", "C"),
+        _stored_row("p", 50, 0, "A", "C", cryptic=True),
+        _stored_row("n", 5, 0, "N", "A"),
+        _stored_row("big", 0, 0, "A", "C"), _stored_row("big", 64, 0, "A", "C"), _stored_row("big", 2000, 0, "A", "C"),
+        _stored_row("big", 4095, 0, "A", "C", counts={"C": 20, "T": 10}),
+        _stored_row("big", 4096, 0, "A", "C", var="G", allele_count=2)])
+    b_rows = pd.DataFrame([
+        _stored_row("big", 0, 0, "A", "C"), _stored_row("big", 64, 0, "A", "T", counts={"T": 25, "C": 5}),
+        _stored_row("big", 2000, 0, "A", "T"), _stored_row("big", 4095, 0, "A", "T"),
+        _stored_row("big", 4096, 0, "A", "T", var="G", allele_count=2)])
+    st = compare.SampleSet(ctx, names, lengths, min_cov=5, pooling=True)
+    st.add_profile_pooled("a", {"big": a_cov["big"]}, a_rows, mm_values=[0, 1])
+    st.add_profile_pooled("a", {"p": a_cov["p"], "n": a_cov["n"]}, a_rows, mm_values=[0, 1])
+    st.add_profile_pooled("b", b_cov, b_rows)
+    logs = []
+    table = st.compare(min_freq=0.05, logs=logs)
+    m = st.mismatch_locations("a", "b")
+    assert [(r["scaffold"], r["mm"], r["consensus_SNPs"], r["population_SNPs"], r["compared_bases_count"]) for r in table] == \
+        [("p", 0, 2, 2, 100), ("p", 1, 2, 2, 100), ("big", 0, 4, 1, 4097)]
+    assert len(logs) == 1 and "DEBUG FAILURE CompareScaffold n ['a', 'b']" in logs[0]
+    raw = m["raw"]
+    got = list(zip(raw["mm"].tolist(), m["scaffold"].tolist(), m["position"].tolist(), raw["consensus_snp"].tolist(),
+                   raw["population_snp"].tolist(), raw["has_a"].tolist(), raw["has_b"].tolist(), raw["con_a"].tolist(), raw["con_b"].tolist()))
+    assert got == [(0, 0, 10, 1, 1, 1, 0, 3, 0), (0, 0, 50, 1, 1, 1, 0, 1, 0),
+                   (0, 2, 64, 1, 0, 1, 1, 1, 2), (0, 2, 2000, 1, 1, 1, 1, 1, 2), (0, 2, 4095, 1, 0, 1, 1, 1, 2), (0, 2, 4096, 1, 0, 1, 1, 1, 2),
+                   (1, 0, 10, 1, 1, 1, 0, 3, 0), (1, 0, 50, 1, 1, 1, 0, 1, 0)]
+    assert raw["cnt_a"][0].tolist() == [0, 0, 0, 20] and raw["cnt_b"][2].tolist() == [0, 5, 25, 0] and raw["cnt_a"][4].tolist() == [0, 20, 10, 0]
+    # pooling: the sites are the positions of the rows that are not cryptic; a owns them all, b pulls p:10 and n:5 (no reads: zeros)
+    assert st.pool_sites() == 7
+    off = st.offsets
+    assert st.pool_site_positions().tolist() == [off[0] + 10, off[1] + 5] + [off[2] + p for p in (0, 64, 2000, 4095, 4096)]
+    assert st.pool_plan("a") == {} and st.pool_plan("b") == {"p": (9, 11, 1), "n": (4, 6, 1)}
+    st.pool_obs_done("b")
+    st.pooled_tables()
+    counts, meta = st.pool_raw["counts"], st.pool_raw["meta"]
+    st.close()
+    assert counts[0].tolist() == [[0, 20, 0, 0], [20, 0, 0, 0], [0, 20, 0, 0], [0, 20, 0, 0], [0, 20, 0, 0], [0, 20, 10, 0], [0, 20, 0, 0]]
+    assert counts[1].tolist() == [[0, 0, 0, 0], [0, 0, 0, 0], [0, 20, 0, 0], [0, 5, 25, 0], [0, 0, 20, 0], [0, 0, 20, 0], [0, 0, 20, 0]]
+    own = (meta & 2) != 0
+    assert own[0].all() and own[1].tolist() == [False, False] + [True] * 5 and (meta & 1).all()
+    assert ((meta[0] >> 5) & 3).tolist() == [1, 0, 1, 1, 1, 1, 1]          # con_base of a's own rows: p:10 is the mm 0 row's C, not G
+
+
 # ---- 5. refusals ----
 def test_refusals_leave_the_set_as_it_was(ctx, edges):
     from instrain_amd import compare, _lib
