@@ -61,6 +61,9 @@ void isx_set_error(const std::string &msg);
 namespace {
 
 enum { CM = 0, CI, CD, CN, CS, CH, CP, CEQ, CX };
+// what a CIGAR operation consumes: the query (I S), the reference (D N), both (M = X: an aligned run) or neither (H P)
+enum { EATS_Q = 1, EATS_R = 2, EATS_BOTH = 3 };
+constexpr uint8_t OP_EATS[16] = {EATS_BOTH, EATS_Q, EATS_R, EATS_R, EATS_Q, 0, 0, EATS_BOTH, EATS_BOTH, 0, 0, 0, 0, 0, 0, 0};
 constexpr uint16_t FPROPER = 0x2, FUNMAP = 0x4, FMUNMAP = 0x8, FSECONDARY = 0x100, FQCFAIL = 0x200, FDUP = 0x400;
 constexpr uint16_t DEF_MASK = FUNMAP | FSECONDARY | FQCFAIL | FDUP;
 
@@ -365,95 +368,63 @@ struct Inflater {       // one per thread
 inline int32_t rd32(const uint8_t *p) { int32_t v; memcpy(&v, p, 4); return v; }
 inline uint16_t rd16(const uint8_t *p) { uint16_t v; memcpy(&v, p, 2); return v; }
 
-// aux fields of a record: the NM tag; every read is checked against `end`
+// One pass over the aux fields of a record, every read checked against `end`: f(tag, type, value) per field (the value of a B array
+// starts at its subtype; count and elements follow); f returns true to stop there.  1 = stopped, 0 = walked to the end, -1 = malformed
+template <class F>
+int aux_walk(const uint8_t *p, const uint8_t *end, F &&f)
+{
+    auto width = [](char t) -> size_t { return (t == 'c' || t == 'C') ? 1 : (t == 's' || t == 'S') ? 2 : (t == 'i' || t == 'I' || t == 'f') ? 4 : 0; };
+    while (p + 3 <= end) {
+        const uint8_t *tag = p;
+        const char t = (char)p[2];
+        p += 3;
+        size_t step = t == 'A' ? 1 : width(t);
+        if (t == 'Z' || t == 'H') {
+            const uint8_t *q = p;
+            while (q < end && *q) q++;
+            if (q >= end) return -1;
+            step = (size_t)(q - p) + 1;
+        } else if (t == 'B') {
+            if (end - p < 5) return -1;
+            const size_t sz = width((char)p[0]);
+            const int32_t cnt = rd32(p + 1);
+            if (!sz || cnt < 0 || (uint64_t)cnt * sz > (uint64_t)(end - p - 5)) return -1;
+            step = 5 + (size_t)cnt * sz;
+        } else if (!step) return -1;
+        if ((size_t)(end - p) < step) return -1;
+        if (f(tag, t, p)) return 1;
+        p += step;
+    }
+    return p == end ? 0 : -1;
+}
+
+// the NM tag of a record (the last one, when it holds an integer); 0, or -1 on a malformed aux block
 int parse_nm(const uint8_t *p, const uint8_t *end, bool &has, int32_t &nm)
 {
     has = false;
-    while (p + 3 <= end) {
-        const bool is_nm = (p[0] == 'N' && p[1] == 'M');
-        const char t = (char)p[2];
-        p += 3;
-        int64_t v = 0;
-        bool num = true;
-        size_t need = 0;
+    return aux_walk(p, end, [&](const uint8_t *tag, char t, const uint8_t *v) {
+        if (tag[0] != 'N' || tag[1] != 'M') return false;
         switch (t) {
-        case 'A': case 'c': case 'C': need = 1; break;
-        case 's': case 'S': need = 2; break;
-        case 'i': case 'I': case 'f': need = 4; break;
-        case 'Z': case 'H': case 'B': break;
-        default: return -1;
+        case 'c': nm = (int8_t)*v; break;
+        case 'C': nm = *v; break;
+        case 's': nm = (int16_t)rd16(v); break;
+        case 'S': nm = rd16(v); break;
+        case 'i': case 'I': nm = rd32(v); break;
+        default: return false;
         }
-        if ((size_t)(end - p) < need) return -1;
-        switch (t) {
-        case 'A': v = *p; p += 1; num = false; break;
-        case 'c': v = (int8_t)*p; p += 1; break;
-        case 'C': v = *p; p += 1; break;
-        case 's': { int16_t x; memcpy(&x, p, 2); v = x; p += 2; break; }
-        case 'S': { uint16_t x; memcpy(&x, p, 2); v = x; p += 2; break; }
-        case 'i': { int32_t x; memcpy(&x, p, 4); v = x; p += 4; break; }
-        case 'I': { uint32_t x; memcpy(&x, p, 4); v = x; p += 4; break; }
-        case 'f': p += 4; num = false; break;
-        case 'Z': case 'H':
-            while (p < end && *p) p++;
-            if (p >= end) return -1;
-            p++; num = false; break;
-        case 'B': {
-            if (end - p < 5) return -1;
-            const char sub = (char)p[0];
-            const int32_t cnt = rd32(p + 1);
-            int sz;
-            switch (sub) {
-            case 'c': case 'C': sz = 1; break;
-            case 's': case 'S': sz = 2; break;
-            case 'i': case 'I': case 'f': sz = 4; break;
-            default: return -1;
-            }
-            if (cnt < 0 || (uint64_t)cnt * sz > (uint64_t)(end - p - 5)) return -1;
-            p += 5 + (size_t)cnt * sz;
-            num = false;
-            break;
-        }
-        }
-        if (is_nm && num) { has = true; nm = (int32_t)v; }
-    }
-    return p == end ? 0 : -1;
+        has = true;
+        return false;
+    });
 }
 
 // the CG:B,I tag of a record: 1 and the operations when present, 0 when absent, -1 on a malformed aux block
 int find_long_cigar(const uint8_t *p, const uint8_t *end, const uint8_t *&ops, uint32_t &n_ops)
 {
-    while (p + 3 <= end) {
-        const bool is_cg = (p[0] == 'C' && p[1] == 'G');
-        const char t = (char)p[2];
-        p += 3;
-        size_t step = 0;
-        switch (t) {
-        case 'A': case 'c': case 'C': step = 1; break;
-        case 's': case 'S': step = 2; break;
-        case 'i': case 'I': case 'f': step = 4; break;
-        case 'Z': case 'H': {
-            const uint8_t *q = p;
-            while (q < end && *q) q++;
-            if (q >= end) return -1;
-            step = (size_t)(q - p) + 1;
-            break;
-        }
-        case 'B': {
-            if (end - p < 5) return -1;
-            const char sub = (char)p[0];
-            const int32_t cnt = rd32(p + 1);
-            const int sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-            if (!sz || cnt < 0 || (uint64_t)cnt * sz > (uint64_t)(end - p - 5)) return -1;
-            if (is_cg && sub == 'I') { ops = p + 5; n_ops = (uint32_t)cnt; return 1; }
-            step = 5 + (size_t)cnt * sz;
-            break;
-        }
-        default: return -1;
-        }
-        if ((size_t)(end - p) < step) return -1;
-        p += step;
-    }
-    return p == end ? 0 : -1;
+    return aux_walk(p, end, [&](const uint8_t *tag, char t, const uint8_t *v) {
+        if (tag[0] != 'C' || tag[1] != 'G' || t != 'B' || v[0] != 'I') return false;
+        ops = v + 5; n_ops = (uint32_t)rd32(v + 1);
+        return true;
+    });
 }
 
 uint64_t hash_name(const uint8_t *s, size_t n)
@@ -543,15 +514,46 @@ void par_assign(isxenc::HostPool &pool, uvec<T> &v, size_t n, T x)
     if (n_tasks > 1) pool.run(n_tasks, body); else if (n_tasks == 1) body(0);
 }
 
+// n items over the pool in pieces of about `grain`: nt tasks (at most four a thread), task t takes the items [lo(t), lo(t + 1))
+struct Slices {
+    size_t n;
+    int nt;
+    Slices(const isxenc::HostPool &pool, size_t n_, size_t grain)
+        : n(n_), nt((int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n_ / grain + 1))) {}
+    size_t lo(int t) const { return n * (size_t)t / (size_t)nt; }
+};
+
+// iterate_splits (fasta.py:56-73) of a scaffold of sLen > 0 columns at window length W: n splits of `chunk` columns, the last one
+// up to the scaffold's end (the division is the reference's: in floating point, truncated)
+struct Splits {
+    int64_t sLen, n, chunk;
+    Splits(int64_t sLen_, int64_t W) : sLen(sLen_), n(sLen_ / W + 1), chunk((int64_t)((double)sLen_ / (double)n)) {}
+    int64_t start(int64_t c) const { return c * chunk; }
+    int64_t end(int64_t c) const { return c + 1 == n ? sLen - 1 : (c + 1) * chunk - 1; }           // inclusive
+    int64_t of(int64_t pos) const { return chunk > 0 ? std::min<int64_t>(pos / chunk, n - 1) : 0; }
+};
+inline int64_t window_length_of(const isx_bam_params &p) { return p.window_length > 0 ? p.window_length : 10000; }
+
+// a parallel stage failed with `rc`: the first text its work items (strings, or structs with an `err`) left behind is the error
+inline const std::string &err_text(const std::string &s) { return s; }
+template <class W> const std::string &err_text(const W &w) { return w.err; }
+template <class Items>
+int hand_back_error(int rc, const Items &items)
+{
+    for (const auto &w : items) if (!err_text(w).empty()) { isx_set_error(err_text(w)); break; }
+    return rc;
+}
+
 // stable bucketing of the indices [0, n) by key(i) in [0, P): order lists bucket 0's indices ascending, then bucket 1's, ...
 template <class Key>
 void bucket_indices(isxenc::HostPool &pool, size_t n, int P, Key key, std::vector<uint32_t> &order, std::vector<size_t> &start)
 {
-    const int C = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n / 65536 + 1));
+    const Slices sl(pool, n, 65536);
+    const int C = sl.nt;
     std::vector<size_t> cnt((size_t)C * (size_t)P, 0);
     pool.run(C, [&](int c) {
         size_t *k = cnt.data() + (size_t)c * (size_t)P;
-        for (size_t i = n * (size_t)c / (size_t)C; i < n * ((size_t)c + 1) / (size_t)C; i++) { const int b = key(i); if (b >= 0) k[b]++; }
+        for (size_t i = sl.lo(c); i < sl.lo(c + 1); i++) { const int b = key(i); if (b >= 0) k[b]++; }
     });
     start.assign((size_t)P + 1, 0);
     size_t at = 0;
@@ -563,7 +565,7 @@ void bucket_indices(isxenc::HostPool &pool, size_t n, int P, Key key, std::vecto
     order.resize(at);
     pool.run(C, [&](int c) {
         size_t *k = cnt.data() + (size_t)c * (size_t)P;
-        for (size_t i = n * (size_t)c / (size_t)C; i < n * ((size_t)c + 1) / (size_t)C; i++) { const int b = key(i); if (b >= 0) order[k[b]++] = (uint32_t)i; }
+        for (size_t i = sl.lo(c); i < sl.lo(c + 1); i++) { const int b = key(i); if (b >= 0) order[k[b]++] = (uint32_t)i; }
     });
 }
 
@@ -815,8 +817,6 @@ struct RecView {        // validated fixed part of a record
     const uint8_t *name, *cigar, *seq, *qual, *aux, *end;
 };
 
-int find_long_cigar(const uint8_t *p, const uint8_t *end, const uint8_t *&ops, uint32_t &n_ops);
-
 bool rec_view(const uint8_t *p, RecView &r)
 {
     r.p = p;
@@ -861,22 +861,18 @@ RefSpan span_of(const uint8_t *cigar, int n_cigar, int32_t pos)
     for (int k = 0; k < n_cigar; k++) {
         uint32_t c;
         memcpy(&c, cigar + 4 * (size_t)k, 4);
-        const int op = c & 15;
+        const int eats = OP_EATS[c & 15];
         const int64_t n = c >> 4;
-        if (op == CM || op == CEQ || op == CX) {
-            if (n > 0) {
-                if (!s.any) { s.first = ref; s.any = true; }
-                s.last = ref + n - 1;
-            }
-            ref += n;
-        } else if (op == CD || op == CN) ref += n;
-        if (op == CM || op == CI || op == CS || op == CEQ || op == CX) s.qlen += n;
+        if (eats == EATS_BOTH && n > 0) {
+            if (!s.any) { s.first = ref; s.any = true; }
+            s.last = ref + n - 1;
+        }
+        if (eats & EATS_R) ref += n;
+        if (eats & EATS_Q) s.qlen += n;
     }
     s.end = ref;
     return s;
 }
-
-int n_threads_default();
 
 // One BGZF block header at `off`: 0 = not one (or it reaches beyond the file), else the block's size; hdr / isize filled in.
 inline size_t bgzf_header_at(const uint8_t *map, size_t map_len, size_t off, uint32_t &hdr, uint32_t &isize)
@@ -1000,14 +996,13 @@ int open_file(const char *path, isx_bam &B)
     return ISX_OK;
 }
 
-// htslib sam.c tweak_overlap_quality on two reads of the batch
-struct SegBuf;
 struct Batch {
     uvec<Read> reads;
     RawBuf<uint32_t> cigars;                // copied (aligned); sequences and qualities stay in the inflated segments:
     std::vector<uvec<uint8_t>> seg_data;
 };
 
+// htslib sam.c tweak_overlap_quality on two reads of the batch
 void tweak_overlap(Batch &S, const Read &a, const Read &b)
 {
     Cursor ca{S.cigars.data() + a.cigar_off, (int)a.n_cigar, 0, 0, 0, 0};
@@ -1252,165 +1247,189 @@ int isx_bam_set_priority_reads(isx_bam *bam, int64_t n, const char *names, const
     return ISX_OK;
 }
 
-// ---- pass 1: get_paired_reads for every reference (filter_reads.py:885-956) ----
-int isx_bam_scan(isx_bam *bam, isx_bam_info *info) { return isx_bam_scan_part(bam, 0, 1, info); }
+}  // extern "C"
 
-// Pass 1 over ONE of n_parts shares of the file (ranks of a multi-GPU run: each scans its share, not the whole file).
-// The share is a range of segments of equal compressed size, [s0, s1); the handle OWNS the references whose first read lies in
-// it: their pair tables are complete (the scan runs on past s1 until the reference that straddles it has ended), every other
-// reference looks empty to this handle.  A share that does not start the file begins two segments early: the chain check
-// (a segment's first record must be where the previous segment's walk ended) then holds for its own first segment exactly
-// as in a whole-file scan, and the last read before s0 tells whether the reference at s0 began earlier (then it belongs to the
-// previous share).  What is global -- the median insert of the read filter -- is the caller's to combine
-// (isx_bam_insert_sizes of every share -> isx_bam_filter(median_insert)).
-int isx_bam_scan_part(isx_bam *bam, int32_t part, int32_t n_parts, isx_bam_info *info)
+// ---- pass 1: get_paired_reads for every reference (filter_reads.py:885-956); isx_bam_scan_part is a driver over these stages ----
+namespace {
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Scan {               // what the stages of one share's scan share
+    isx_bam &B;
+    isxenc::HostPool &pool;
+    int32_t part, n_parts;
+    size_t n_ref, n_seg;
+    size_t s0, s1;                      // the share: segments [s0, s1)
+    size_t sv;                          // where the walk starts (verification run-in)
+    size_t s_end;                       // one past the last segment scanned
+    bool have_first;                    // the file's first record is known; any other start is a guess until the chain confirms it
+    bool verified;                      // a guessed start counts once a later segment's own guess falls on the chain walked from it
+    uint64_t first, read_ord = 0;       // where the next record starts; reads walked so far
+    bool keep_inflated = false;
+    std::vector<std::string> errs;      // per segment
+    // ISX_BAM_TIMING (tuning aid: stage times on stderr, no effect on results)
+    bool timing = false;
+    double t_begin = 0, t_mark = 0, t_inflate = 0, t_hop = 0, t_extract = 0, t_bucket = 0, t_tables = 0;
+    std::atomic<uint64_t> thr_guess_us{0}, thr_inflate_us{0}, thr_hop_us{0};       // summed over the pool's threads: block decode / guess + record walk
+    void lap(double &acc) { const double t = now_ms(); acc += t - t_mark; t_mark = t; }
+};
+
+struct Wave {               // the segments [w0, w1) in flight
+    size_t w0, w1;
+    std::vector<SegBuf> bufs;
+    std::vector<std::vector<uint64_t>> recs;
+    std::vector<uint64_t> guess, nexts;
+    std::vector<int> hop_rc, lite_rc;               // lite_rc OK: the sweep extracted every record of its walk
+    Wave(size_t a, size_t b) : w0(a), w1(b), bufs(b - a), recs(b - a), guess(b - a, ~0ull), nexts(b - a, 0), hop_rc(b - a, ISX_OK), lite_rc(b - a, ISX_ERR_STATE) {}
+};
+
+// ... then the chain is checked serially: a segment's first record must be where the previous segment's walk
+// ended; where the guess was off (or there was none) that segment is walked again from the right place
+int wave_check_chain(Scan &X, Wave &W)
 {
-    if (!bam || n_parts < 1 || part < 0 || part >= n_parts) { isx_set_error("isx_bam_scan: bad argument"); return ISX_ERR_ARG; }
-    isx_bam &B = *bam;
-    if (B.scanned) {
-        if (B.part != part || B.n_parts != n_parts) { isx_set_error("isx_bam_scan: this handle already scanned another share of the file"); return ISX_ERR_STATE; }
-        if (info) *info = B.totals;
-        return ISX_OK;
+    isx_bam &B = X.B;
+    Inflater inf;
+    for (size_t si = W.w0; si < W.w1; si++) {
+        Segment &s = B.segs[si];
+        const size_t k = si - W.w0;
+        auto no_record_starts = [&] { s.first_rec = s.ioff1; s.read0 = X.read_ord; s.n_reads = 0; W.recs[k].clear(); W.lite_rc[k] = ISX_ERR_STATE; };
+        if (!X.have_first) {                // a share's run-in: start from the structural guess
+            if (W.guess[k] == ~0ull) { no_record_starts(); continue; }
+            X.first = W.guess[k];
+            X.have_first = true;
+        }
+        if (X.first > s.ioff1) { no_record_starts(); continue; }        // a record spans the whole segment
+        s.first_rec = std::max(X.first, s.ioff0);
+        if (!X.verified && s.first_rec < s.ioff1 && W.guess[k] != ~0ull && si > X.sv) {
+            // the run-in of a share: the chain started from a structural guess.  The next segment's own, independent guess
+            // either falls on the chain -- both are right -- or one of them is wrong and nothing here can tell which
+            if (W.guess[k] != s.first_rec) {
+                isx_set_error("isx_bam_scan_part: the record chain walked from a guessed start disagrees with the next segment's own guess: scan the whole file instead");
+                return ISX_ERR_IO;
+            }
+            X.verified = true;
+        }
+        if (!X.verified && si >= X.s0 && X.n_parts > 1) {
+            isx_set_error("isx_bam_scan_part: no second record start confirmed the guessed one in the two segments before this share: scan the whole file instead");
+            return ISX_ERR_IO;
+        }
+        uint64_t next = X.first;
+        if (s.first_rec >= s.ioff1) { W.recs[k].clear(); W.lite_rc[k] = ISX_ERR_STATE; }
+        else if (W.guess[k] == s.first_rec && W.hop_rc[k] == ISX_OK) next = W.nexts[k];
+        else {
+            W.lite_rc[k] = ISX_ERR_STATE;       // (the sweep walked -- and extracted -- from a wrong start)
+            const int rc = seg_hop(B, inf, s, W.bufs[k], s.first_rec, W.recs[k], next);
+            if (rc != ISX_OK) return rc;
+        }
+        s.read0 = X.read_ord; s.n_reads = (uint32_t)W.recs[k].size();
+        X.read_ord += s.n_reads;
+        X.first = next;
     }
-    B.part = part; B.n_parts = n_parts;
-    isxenc::HostPool &pool = pool_of(B);
-    const size_t n_ref = B.ref_name.size(), n_seg = B.segs.size();
-    const bool timing = getenv("ISX_BAM_TIMING") != nullptr;       // tuning aid: stage times on stderr (no effect on results)
-    double t_inflate = 0, t_hop = 0, t_extract = 0;
-    std::atomic<uint64_t> thr_guess_us{0};
-    std::atomic<uint64_t> thr_inflate_us{0}, thr_hop_us{0};        // (timing only) summed over the pool's threads: block decode / guess + record walk
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    double t_mark = t_begin;
-    B.seg_reads.assign(n_seg, {}); B.seg_names.assign(n_seg, {});
-    // pass 2 needs the same bytes again: keep a file's inflated segments when they are a small part of what the host has free
-    const bool keep_inflated = B.total_inflated <= inflate_cache_limit();
-    if (keep_inflated) { B.seg_cache.assign(n_seg, {}); B.seg_cache_rec.assign(n_seg, {}); }
-    // waves of segments: inflate (parallel) -> record boundaries (serial walk over block_size fields) -> field
-    // extraction (parallel).  At most one wave of inflated data is alive.
-    // (ISX_BAM_WAVE / ISX_BAM_SEG_KIB: tuning aids.  Round 5 tried several small segments per thread and wave, handed out one at a time --
-    //  256 segments in waves of 64 instead of 128 in waves of 16 -- against the 15 % a wave loses to its slowest decode: 249-276 ms
-    //  against 193-307 for the scan of the probe on one (noisy) box and a slower pass 2; not kept)
-    size_t wave = (size_t)std::max(2, pool.size());
+    return ISX_OK;
+}
+
+// reference of the last read that starts before segment `s`, looking back as far as the scan's first segment; -2: there is none
+int32_t tid_before(const Scan &X, size_t s)
+{
+    for (size_t si = s; si-- > X.sv;) if (!X.B.seg_reads[si].empty()) return X.B.seg_reads[si].back().tid;
+    return -2;
+}
+
+// past the share, segments up to w1 scanned: has the reference that straddles s1 ended (a read of another reference, or an
+// unmapped one, was seen at or after s1)?
+bool straddler_ended(const Scan &X, size_t w1)
+{
+    const isx_bam &B = X.B;
+    const int32_t t_end = tid_before(X, X.s1);
+    if (t_end < 0) return true;
+    if (X.s0 > 0) {                         // a share inside one long scaffold owns nothing: nothing to complete either
+        const int32_t t_prev = tid_before(X, X.s0);
+        bool owns_any = false;
+        for (size_t si = X.s0; si < X.s1 && !owns_any; si++)
+            for (const ReadLite &L : B.seg_reads[si]) if (L.tid >= 0 && L.tid != t_prev) { owns_any = true; break; }
+        if (!owns_any) return true;
+    }
+    for (size_t si = X.s1; si < w1; si++)
+        if (!B.seg_reads[si].empty() && B.seg_reads[si].back().tid != t_end) return true;
+    return false;
+}
+
+// waves of segments: inflate (parallel) -> record boundaries (serial walk over block_size fields) -> field
+// extraction (parallel).  At most one wave of inflated data is alive.
+// (ISX_BAM_WAVE / ISX_BAM_SEG_KIB: tuning aids.  Round 5 tried several small segments per thread and wave, handed out one at a time --
+//  256 segments in waves of 64 instead of 128 in waves of 16 -- against the 15 % a wave loses to its slowest decode: 249-276 ms
+//  against 193-307 for the scan of the probe on one (noisy) box and a slower pass 2; not kept)
+int scan_waves(Scan &X)
+{
+    isx_bam &B = X.B;
+    size_t wave = (size_t)std::max(2, X.pool.size());
     if (const char *e = getenv("ISX_BAM_WAVE")) wave = (size_t)std::max(2, atoi(e));
-    uint64_t first = B.first_rec, read_ord = 0;
-    std::vector<std::string> errs(n_seg);
-    const size_t s0 = n_seg * (size_t)part / (size_t)n_parts, s1 = n_seg * ((size_t)part + 1) / (size_t)n_parts;
-    size_t sv = s0 >= 2 ? s0 - 2 : 0;           // where the walk starts (verification run-in)
-    bool have_first = sv == 0;                  // the file's first record is known; any other start is a guess until the chain confirms it
-    bool verified = sv == 0;                    // a guessed start counts once a later segment's own guess falls on the chain walked from it
-    size_t s_end = n_seg;                       // one past the last segment scanned
-    if (s0 == s1) { sv = 0; s_end = 0; }        // more shares than segments: this one is empty
-    for (size_t w0 = sv, w1 = 0; w0 < s_end; w0 = w1) {
+    for (size_t w0 = X.sv, w1 = 0; w0 < X.s_end; w0 = w1) {
         // full waves while they start inside the share; past its end a quarter wave at a time (the scaffold that straddles
         // s1 usually ends within a segment or two)
-        w1 = std::min(n_seg, w0 + ((n_parts > 1 && w0 >= s1) ? std::max<size_t>(1, wave / 4) : wave));
-        std::vector<SegBuf> bufs(w1 - w0);
-        std::vector<std::vector<uint64_t>> recs(w1 - w0);
-        std::atomic<int> bad{0};
+        w1 = std::min(X.n_seg, w0 + ((X.n_parts > 1 && w0 >= X.s1) ? std::max<size_t>(1, wave / 4) : wave));
+        Wave W(w0, w1);
         // every segment: inflate, guess where its first record starts, walk its records from there (all in parallel) ...
-        std::vector<uint64_t> guess(w1 - w0, ~0ull), nexts(w1 - w0, 0);
-        std::vector<int> hop_rc(w1 - w0, ISX_OK), lite_rc(w1 - w0, ISX_ERR_STATE);      // lite_rc OK: the sweep extracted every record of its walk
-        pool.run((int)(w1 - w0), [&](int i) {
+        std::atomic<int> bad{0};
+        X.pool.run((int)(w1 - w0), [&](int i) {
             Inflater inf;
             const Segment &s = B.segs[w0 + (size_t)i];
-            const double ta = timing ? now() : 0.0;
+            const double ta = X.timing ? now_ms() : 0.0;
             const bool is_first = w0 + (size_t)i == 0;
             uint64_t g = is_first ? std::max(B.first_rec, s.ioff0) : ~0ull;
             if (is_first && B.first_rec > s.ioff1) g = ~0ull;
             const bool do_guess = !is_first;
-            if (!seg_inflate_hop(B, inf, s, bufs[(size_t)i], g, do_guess, &g, recs[(size_t)i], nexts[(size_t)i], &hop_rc[(size_t)i],
-                                 &B.seg_reads[w0 + (size_t)i], &B.seg_names[w0 + (size_t)i], &lite_rc[(size_t)i])) { bad.store(1); return; }
-            guess[(size_t)i] = g;
-            const double tb = timing ? now() : 0.0, tg = tb;
-            if (timing) { const double tc = now(); thr_inflate_us.fetch_add((uint64_t)((tb - ta) * 1e3)); thr_hop_us.fetch_add((uint64_t)((tc - tb) * 1e3)); thr_guess_us.fetch_add((uint64_t)((tg - tb) * 1e3)); }
+            if (!seg_inflate_hop(B, inf, s, W.bufs[(size_t)i], g, do_guess, &g, W.recs[(size_t)i], W.nexts[(size_t)i], &W.hop_rc[(size_t)i],
+                                 &B.seg_reads[w0 + (size_t)i], &B.seg_names[w0 + (size_t)i], &W.lite_rc[(size_t)i])) { bad.store(1); return; }
+            W.guess[(size_t)i] = g;
+            const double tb = X.timing ? now_ms() : 0.0, tg = tb;
+            if (X.timing) { const double tc = now_ms(); X.thr_inflate_us.fetch_add((uint64_t)((tb - ta) * 1e3)); X.thr_hop_us.fetch_add((uint64_t)((tc - tb) * 1e3)); X.thr_guess_us.fetch_add((uint64_t)((tg - tb) * 1e3)); }
         });
         if (bad.load()) { isx_set_error("BGZF inflate failed"); return ISX_ERR_IO; }
-        { const double t = now(); t_inflate += t - t_mark; t_mark = t; }
-        // ... then the chain is checked serially: a segment's first record must be where the previous segment's walk
-        // ended; where the guess was off (or there was none) that segment is walked again from the right place
-        Inflater inf;
-        for (size_t si = w0; si < w1; si++) {
-            Segment &s = B.segs[si];
-            const size_t k = si - w0;
-            if (!have_first) {                  // a share's run-in: start from the structural guess
-                if (guess[k] == ~0ull) { s.first_rec = s.ioff1; s.read0 = read_ord; s.n_reads = 0; recs[k].clear(); lite_rc[k] = ISX_ERR_STATE; continue; }
-                first = guess[k];
-                have_first = true;
-            }
-            if (first > s.ioff1) { s.first_rec = s.ioff1; s.read0 = read_ord; s.n_reads = 0; recs[k].clear(); lite_rc[k] = ISX_ERR_STATE; continue; }    // a record spans the whole segment
-            s.first_rec = std::max(first, s.ioff0);
-            if (!verified && s.first_rec < s.ioff1 && guess[k] != ~0ull && si > sv) {
-                // the run-in of a share: the chain started from a structural guess.  The next segment's own, independent guess
-                // either falls on the chain -- both are right -- or one of them is wrong and nothing here can tell which
-                if (guess[k] != s.first_rec) {
-                    isx_set_error("isx_bam_scan_part: the record chain walked from a guessed start disagrees with the next segment's own guess: scan the whole file instead");
-                    return ISX_ERR_IO;
-                }
-                verified = true;
-            }
-            if (!verified && si >= s0 && n_parts > 1) {
-                isx_set_error("isx_bam_scan_part: no second record start confirmed the guessed one in the two segments before this share: scan the whole file instead");
-                return ISX_ERR_IO;
-            }
-            uint64_t next = first;
-            if (s.first_rec >= s.ioff1) { recs[k].clear(); lite_rc[k] = ISX_ERR_STATE; next = first; }
-            else if (guess[k] == s.first_rec && hop_rc[k] == ISX_OK) next = nexts[k];
-            else {
-                lite_rc[k] = ISX_ERR_STATE;         // (the sweep walked -- and extracted -- from a wrong start)
-                const int rc = seg_hop(B, inf, s, bufs[k], s.first_rec, recs[k], next);
-                if (rc != ISX_OK) return rc;
-            }
-            s.read0 = read_ord; s.n_reads = (uint32_t)recs[k].size();
-            read_ord += s.n_reads;
-            first = next;
-        }
-        { const double t = now(); t_hop += t - t_mark; t_mark = t; }
+        X.lap(X.t_inflate);
+        const int rc = wave_check_chain(X, W);
+        if (rc != ISX_OK) return rc;
+        X.lap(X.t_hop);
         std::atomic<int> rc_any{0};
-        pool.run((int)(w1 - w0), [&](int i) {
-            if (lite_rc[(size_t)i] == ISX_OK && B.seg_reads[w0 + (size_t)i].size() == recs[(size_t)i].size() && !getenv("ISX_BAM_NO_FUSED_EXTRACT")) return;   // done in the sweep
-            const int rc = scan_segment(B, (uint32_t)(w0 + (size_t)i), bufs[(size_t)i], recs[(size_t)i], errs[w0 + (size_t)i]);
+        X.pool.run((int)(w1 - w0), [&](int i) {
+            if (W.lite_rc[(size_t)i] == ISX_OK && B.seg_reads[w0 + (size_t)i].size() == W.recs[(size_t)i].size() && !getenv("ISX_BAM_NO_FUSED_EXTRACT")) return;   // done in the sweep
+            const int rc = scan_segment(B, (uint32_t)(w0 + (size_t)i), W.bufs[(size_t)i], W.recs[(size_t)i], X.errs[w0 + (size_t)i]);
             if (rc != ISX_OK) rc_any.store(rc);
         });
-        if (rc_any.load()) { for (auto &e : errs) if (!e.empty()) { isx_set_error(e); break; } return rc_any.load(); }
-        if (keep_inflated)
-            for (size_t si = w0; si < w1; si++) { B.seg_cache[si].swap(bufs[si - w0].data); B.seg_cache_rec[si].swap(recs[si - w0]); }
-        { const double t = now(); t_extract += t - t_mark; t_mark = t; }
-        if (n_parts > 1 && w1 >= s1 && w1 < n_seg) {
-            // past the share: stop once the reference that straddles s1 has ended (a read of another reference, or an
-            // unmapped one, was seen at or after s1)
-            int32_t t_end = -2;
-            for (size_t si = s1; si-- > sv;) if (!B.seg_reads[si].empty()) { t_end = B.seg_reads[si].back().tid; break; }
-            bool ended = t_end < 0;
-            if (!ended && s0 > 0) {             // a share inside one long scaffold owns nothing: nothing to complete either
-                int32_t t_prev = -2;
-                for (size_t si = s0; si-- > sv;) if (!B.seg_reads[si].empty()) { t_prev = B.seg_reads[si].back().tid; break; }
-                bool owns_any = false;
-                for (size_t si = s0; si < s1 && !owns_any; si++)
-                    for (const ReadLite &L : B.seg_reads[si]) if (L.tid >= 0 && L.tid != t_prev) { owns_any = true; break; }
-                if (!owns_any) ended = true;
-            }
-            for (size_t si = s1; si < w1 && !ended; si++)
-                if (!B.seg_reads[si].empty() && B.seg_reads[si].back().tid != t_end) ended = true;
-            if (ended) { s_end = w1; break; }
-        }
+        if (rc_any.load()) return hand_back_error(rc_any.load(), X.errs);
+        if (X.keep_inflated)
+            for (size_t si = w0; si < w1; si++) { B.seg_cache[si].swap(W.bufs[si - w0].data); B.seg_cache_rec[si].swap(W.recs[si - w0]); }
+        X.lap(X.t_extract);
+        // past the share: stop once the reference that straddles s1 has ended
+        if (X.n_parts > 1 && w1 >= X.s1 && w1 < X.n_seg && straddler_ended(X, w1)) { X.s_end = w1; break; }
     }
-    if (s_end == n_seg && s0 != s1 && first != B.total_inflated) { isx_set_error("truncated BAM record"); return ISX_ERR_IO; }
-    B.n_reads = read_ord;
-    // which references this share owns: those whose first read lies in [s0, s1)
-    std::vector<uint8_t> owned(n_ref, n_parts == 1 ? 1 : 0);
-    if (n_parts > 1 && s0 != s1) {
-        int32_t t_prev = -2;                    // reference of the last read before s0: its run began in an earlier share
-        for (size_t si = s0; si-- > sv;) if (!B.seg_reads[si].empty()) { t_prev = B.seg_reads[si].back().tid; break; }
-        if (s0 > 0 && t_prev == -2) { isx_set_error("isx_bam_scan_part: no record starts in the two segments before this share (a record longer than a segment): scan the whole file instead"); return ISX_ERR_ARG; }
-        for (size_t si = s0; si < s1; si++)
-            for (const ReadLite &L : B.seg_reads[si]) if (L.tid >= 0 && L.tid != t_prev) owned[(size_t)L.tid] = 1;
-    }
-    // per segment on the threads: the longest reference span of a read, and the runs of reads of one reference
-    struct TidRun { int32_t tid; uint32_t i0, i1; };
-    std::vector<std::vector<TidRun>> seg_runs(n_seg);
-    std::vector<int64_t> seg_span(n_seg, 0);
-    pool.run((int)n_seg, [&](int k) {
+    if (X.s_end == X.n_seg && X.s0 != X.s1 && X.first != B.total_inflated) { isx_set_error("truncated BAM record"); return ISX_ERR_IO; }
+    B.n_reads = X.read_ord;
+    return ISX_OK;
+}
+
+// which references this share owns: those whose first read lies in [s0, s1)
+int owned_refs(const Scan &X, std::vector<uint8_t> &owned)
+{
+    owned.assign(X.n_ref, X.n_parts == 1 ? 1 : 0);
+    if (X.n_parts == 1 || X.s0 == X.s1) return ISX_OK;
+    const int32_t t_prev = tid_before(X, X.s0);             // reference of the last read before s0: its run began in an earlier share
+    if (X.s0 > 0 && t_prev == -2) { isx_set_error("isx_bam_scan_part: no record starts in the two segments before this share (a record longer than a segment): scan the whole file instead"); return ISX_ERR_ARG; }
+    for (size_t si = X.s0; si < X.s1; si++)
+        for (const ReadLite &L : X.B.seg_reads[si]) if (L.tid >= 0 && L.tid != t_prev) owned[(size_t)L.tid] = 1;
+    return ISX_OK;
+}
+
+struct TidRun { int32_t tid; uint32_t i0, i1; };            // reads [i0, i1) of a segment: one reference's
+struct Run { uint32_t seg; uint32_t i0, i1; };
+
+// per segment on the threads: its first / last record, the runs of reads of one reference, and the longest reference span of a read
+void segment_runs(Scan &X, std::vector<std::vector<TidRun>> &seg_runs)
+{
+    isx_bam &B = X.B;
+    seg_runs.assign(X.n_seg, {});
+    std::vector<int64_t> seg_span(X.n_seg, 0);
+    X.pool.run((int)X.n_seg, [&](int k) {
         const size_t si = (size_t)k;
         const auto &rs = B.seg_reads[si];
         if (rs.empty()) return;
@@ -1426,89 +1445,106 @@ int isx_bam_scan_part(isx_bam *bam, int32_t part, int32_t n_parts, isx_bam_info 
         seg_runs[si].push_back(TidRun{rs[i0].tid, (uint32_t)i0, (uint32_t)rs.size()});
         seg_span[si] = span;
     });
-    for (size_t si = 0; si < n_seg; si++) B.max_span = std::max(B.max_span, seg_span[si]);
+    for (size_t si = 0; si < X.n_seg; si++) B.max_span = std::max(B.max_span, seg_span[si]);
+}
 
-    // ---- reference -> the run of reads that belongs to it (the file is sorted: a reference's reads are contiguous) ----
-    struct Run { uint32_t seg; uint32_t i0, i1; };
-    std::vector<std::vector<Run>> runs(n_ref);
-    B.ref_seg0.assign(n_ref, 0xFFFFFFFFu); B.ref_seg1.assign(n_ref, 0);
-    B.ref_reads.assign(n_ref, 0);
-    {
-        int32_t last_tid = -2;
-        bool unsorted = false;
-        std::vector<uint8_t> closed(n_ref, 0);
-        for (uint32_t si = 0; si < n_seg; si++) {
-            for (const TidRun &tr : seg_runs[si]) {
-                const int32_t t = tr.tid;
-                const size_t i = tr.i0, j = tr.i1;
-                if (t >= 0 && owned[(size_t)t]) {
-                    if (t != last_tid && closed[(size_t)t]) unsorted = true;
-                    runs[(size_t)t].push_back(Run{si, (uint32_t)i, (uint32_t)j});
-                    B.ref_seg0[(size_t)t] = std::min(B.ref_seg0[(size_t)t], si);
-                    B.ref_seg1[(size_t)t] = std::max(B.ref_seg1[(size_t)t], si);
-                    B.ref_reads[(size_t)t] += (int64_t)(j - i);
-                }
-                if (last_tid >= 0 && t != last_tid) closed[(size_t)last_tid] = 1;
-                last_tid = t;
+// reference -> the runs of reads that belong to it (the file is sorted: a reference's reads are contiguous -- checked here)
+int reference_runs(Scan &X, const std::vector<std::vector<TidRun>> &seg_runs, const std::vector<uint8_t> &owned, std::vector<std::vector<Run>> &runs)
+{
+    isx_bam &B = X.B;
+    runs.assign(X.n_ref, {});
+    B.ref_seg0.assign(X.n_ref, 0xFFFFFFFFu); B.ref_seg1.assign(X.n_ref, 0);
+    B.ref_reads.assign(X.n_ref, 0);
+    int32_t last_tid = -2;
+    bool unsorted = false;
+    std::vector<uint8_t> closed(X.n_ref, 0);
+    for (uint32_t si = 0; si < X.n_seg; si++) {
+        for (const TidRun &tr : seg_runs[si]) {
+            const int32_t t = tr.tid;
+            if (t >= 0 && owned[(size_t)t]) {
+                if (t != last_tid && closed[(size_t)t]) unsorted = true;
+                runs[(size_t)t].push_back(Run{si, tr.i0, tr.i1});
+                B.ref_seg0[(size_t)t] = std::min(B.ref_seg0[(size_t)t], si);
+                B.ref_seg1[(size_t)t] = std::max(B.ref_seg1[(size_t)t], si);
+                B.ref_reads[(size_t)t] += (int64_t)(tr.i1 - tr.i0);
             }
+            if (last_tid >= 0 && t != last_tid) closed[(size_t)last_tid] = 1;
+            last_tid = t;
         }
-        if (unsorted) { isx_set_error("BAM is not sorted by reference: the reads of a reference must be contiguous"); return ISX_ERR_IO; }
     }
+    if (unsorted) { isx_set_error("BAM is not sorted by reference: the reads of a reference must be contiguous"); return ISX_ERR_IO; }
+    return ISX_OK;
+}
 
-    // ---- pair tables: one task per (reference, name-hash partition) ----
-    // The reads are first bucketed by partition (two passes over the per-segment runs: count, then fill an index list in
-    // file order), so that a partition's task touches only its own reads -- not every read of the reference.
-    struct Part { uint32_t ref, p, P; uint64_t r0, r1; std::vector<PairInfo> info; std::string no_nm; };
-    struct ReadRef { uint32_t seg, i; };
+// ---- pair tables: one task per (reference, name-hash partition) ----
+struct Part { uint32_t ref, p, P; uint64_t r0, r1; std::vector<PairInfo> info; std::string no_nm; };
+struct ReadRef { uint32_t seg, i; };
+struct FlatRun { uint32_t ref, seg, i0, i1; size_t cur; };
+struct PairParts {
     std::vector<Part> parts;
-    std::vector<size_t> first_part(n_ref + 1, 0);
+    std::vector<size_t> first_part;         // [n_ref + 1] a reference's partitions follow each other
+    std::vector<FlatRun> flat;              // every run of every reference
+    uvec<ReadRef> order;                    // the reads of partition k: order[parts[k].r0 .. r1), in file order
+    uint32_t n_parts_of(uint32_t ref) const { return (uint32_t)(first_part[ref + 1] - first_part[ref]); }
+    static uint32_t part_of(uint64_t h64, uint32_t P) { return P == 1 ? 0u : (uint32_t)((h64 >> 40) % P); }
+};
+
+// The reads are first bucketed by partition (two passes over the per-segment runs: count, then fill an index list in
+// file order), so that a partition's task touches only its own reads -- not every read of the reference.
+void bucket_by_name_partition(Scan &X, const std::vector<std::vector<Run>> &runs, PairParts &T)
+{
+    isx_bam &B = X.B;
+    const size_t n_ref = X.n_ref;
+    T.first_part.assign(n_ref + 1, 0);
     for (size_t t = 0; t < n_ref; t++) {
-        first_part[t] = parts.size();
+        T.first_part[t] = T.parts.size();
         if (!B.ref_reads[t]) continue;
         const uint32_t P = (uint32_t)std::min<int64_t>(4096, B.ref_reads[t] / 16384 + 1);
-        for (uint32_t p = 0; p < P; p++) parts.push_back(Part{(uint32_t)t, p, P, 0, 0, {}, {}});
+        for (uint32_t p = 0; p < P; p++) T.parts.push_back(Part{(uint32_t)t, p, P, 0, 0, {}, {}});
     }
-    first_part[n_ref] = parts.size();
-    struct FlatRun { uint32_t ref, seg, i0, i1; size_t cur; };
-    std::vector<FlatRun> flat;
+    T.first_part[n_ref] = T.parts.size();
     size_t n_cur = 0;
     for (size_t t = 0; t < n_ref; t++)
-        for (const Run &r : runs[t]) { flat.push_back(FlatRun{(uint32_t)t, r.seg, r.i0, r.i1, n_cur}); n_cur += first_part[t + 1] - first_part[t]; }
+        for (const Run &r : runs[t]) { T.flat.push_back(FlatRun{(uint32_t)t, r.seg, r.i0, r.i1, n_cur}); n_cur += T.n_parts_of((uint32_t)t); }
     std::vector<uint64_t> cur(n_cur, 0);
-    auto part_of = [](uint64_t h64, uint32_t P) -> uint32_t { return P == 1 ? 0u : (uint32_t)((h64 >> 40) % P); };
-    pool.run((int)flat.size(), [&](int k) {
-        const FlatRun &f = flat[(size_t)k];
-        const uint32_t P = (uint32_t)(first_part[f.ref + 1] - first_part[f.ref]);
+    X.pool.run((int)T.flat.size(), [&](int k) {
+        const FlatRun &f = T.flat[(size_t)k];
+        const uint32_t P = T.n_parts_of(f.ref);
         const auto &rs = B.seg_reads[f.seg];
         uint64_t *c = cur.data() + f.cur;
-        for (uint32_t i = f.i0; i < f.i1; i++) c[part_of(rs[i].h64, P)]++;
+        for (uint32_t i = f.i0; i < f.i1; i++) c[PairParts::part_of(rs[i].h64, P)]++;
     });
     {   // counts -> write cursors: a partition's reads stay in file order (its runs in order, each run's reads in order)
         uint64_t at = 0;
         size_t k0 = 0;
         for (size_t t = 0; t < n_ref; t++) {
-            const size_t nr = runs[t].size(), P = first_part[t + 1] - first_part[t];
+            const size_t nr = runs[t].size(), P = T.n_parts_of((uint32_t)t);
             for (size_t p = 0; p < P; p++) {
-                parts[first_part[t] + p].r0 = at;
-                for (size_t k = 0; k < nr; k++) { uint64_t &c = cur[flat[k0 + k].cur + p]; const uint64_t n = c; c = at; at += n; }
-                parts[first_part[t] + p].r1 = at;
+                T.parts[T.first_part[t] + p].r0 = at;
+                for (size_t k = 0; k < nr; k++) { uint64_t &c = cur[T.flat[k0 + k].cur + p]; const uint64_t n = c; c = at; at += n; }
+                T.parts[T.first_part[t] + p].r1 = at;
             }
             k0 += nr;
         }
     }
-    uvec<ReadRef> order((size_t)(parts.empty() ? 0 : parts.back().r1));
-    pool.run((int)flat.size(), [&](int k) {
-        const FlatRun &f = flat[(size_t)k];
-        const uint32_t P = (uint32_t)(first_part[f.ref + 1] - first_part[f.ref]);
+    T.order.resize((size_t)(T.parts.empty() ? 0 : T.parts.back().r1));
+    X.pool.run((int)T.flat.size(), [&](int k) {
+        const FlatRun &f = T.flat[(size_t)k];
+        const uint32_t P = T.n_parts_of(f.ref);
         const auto &rs = B.seg_reads[f.seg];
         uint64_t *c = cur.data() + f.cur;
-        for (uint32_t i = f.i0; i < f.i1; i++) order[(size_t)c[part_of(rs[i].h64, P)]++] = ReadRef{f.seg, i};
+        for (uint32_t i = f.i0; i < f.i1; i++) T.order[(size_t)c[PairParts::part_of(rs[i].h64, P)]++] = ReadRef{f.seg, i};
     });
-    std::vector<uint64_t>().swap(cur);
-    const double t_bucket = now();
-    par_assign(pool, B.read_pair, (size_t)B.n_reads, 0xFFFFFFFFu);
-    pool.run((int)parts.size(), [&](int pi) {
-        Part &pt = parts[(size_t)pi];
+}
+
+// every partition's table: per (scaffold, name) the pair record of get_paired_reads; read_pair gets the index LOCAL to the partition
+int build_pair_tables(Scan &X, PairParts &T)
+{
+    isx_bam &B = X.B;
+    const uvec<ReadRef> &order = T.order;
+    par_assign(X.pool, B.read_pair, (size_t)B.n_reads, 0xFFFFFFFFu);
+    X.pool.run((int)T.parts.size(), [&](int pi) {
+        Part &pt = T.parts[(size_t)pi];
         NameTable tab;
         tab.init((size_t)(pt.r1 - pt.r0));
         pt.info.reserve((size_t)(pt.r1 - pt.r0) / 2 + 8);
@@ -1567,48 +1603,115 @@ int isx_bam_scan_part(isx_bam *bam, int32_t part, int32_t n_parts, isx_bam_info 
             B.read_pair[(size_t)(B.segs[rr.seg].read0 + rr.i)] = idx;       // local index for now
         }
     });
-    const double t_tables = now();
-    for (auto &pt : parts) if (!pt.no_nm.empty()) { isx_set_error("read without NM tag: " + pt.no_nm); return ISX_ERR_IO; }
-    // one table: a reference's partitions follow each other
+    for (auto &pt : T.parts) if (!pt.no_nm.empty()) { isx_set_error("read without NM tag: " + pt.no_nm); return ISX_ERR_IO; }
+    return ISX_OK;
+}
+
+// one table: a reference's partitions follow each other
+int merge_pair_tables(Scan &X, PairParts &T)
+{
+    isx_bam &B = X.B;
+    std::vector<Part> &parts = T.parts;
     std::vector<uint64_t> part_base(parts.size() + 1, 0);
     for (size_t i = 0; i < parts.size(); i++) part_base[i + 1] = part_base[i] + parts[i].info.size();
     if (part_base.back() >= 0xFFFFFFFFull) { isx_set_error("more than 2^32 read names"); return ISX_ERR_ARG; }
     B.pairs.resize((size_t)part_base.back());
-    B.ref_pair0.assign(n_ref + 1, 0);
-    for (size_t t = 0; t <= n_ref; t++) B.ref_pair0[t] = part_base[first_part[t]];
-    pool.run((int)parts.size(), [&](int pi) {
+    B.ref_pair0.assign(X.n_ref + 1, 0);
+    for (size_t t = 0; t <= X.n_ref; t++) B.ref_pair0[t] = part_base[T.first_part[t]];
+    X.pool.run((int)parts.size(), [&](int pi) {
         Part &pt = parts[(size_t)pi];
         std::copy(pt.info.begin(), pt.info.end(), B.pairs.begin() + (ptrdiff_t)part_base[(size_t)pi]);
         std::vector<PairInfo>().swap(pt.info);
     });
     // local pair index -> index into the one table, read by read in file order (a read's partition follows from its hash again)
-    pool.run((int)flat.size(), [&](int k) {
-        const FlatRun &f = flat[(size_t)k];
-        const uint32_t P = (uint32_t)(first_part[f.ref + 1] - first_part[f.ref]);
+    X.pool.run((int)T.flat.size(), [&](int k) {
+        const FlatRun &f = T.flat[(size_t)k];
+        const uint32_t P = T.n_parts_of(f.ref);
         const auto &rs = B.seg_reads[f.seg];
-        const uint64_t *pb = part_base.data() + first_part[f.ref];
+        const uint64_t *pb = part_base.data() + T.first_part[f.ref];
         uint32_t *v = B.read_pair.data() + B.segs[f.seg].read0;
         for (uint32_t i = f.i0; i < f.i1; i++)
-            if (v[i] != 0xFFFFFFFFu) v[i] += (uint32_t)pb[part_of(rs[i].h64, P)];
+            if (v[i] != 0xFFFFFFFFu) v[i] += (uint32_t)pb[PairParts::part_of(rs[i].h64, P)];
     });
-    if (timing) fprintf(stderr, "[isx_bam_scan] share %d/%d: segments [%zu, %zu) of %zu, %d threads: inflate %.1f ms, record walk %.1f ms, field extraction %.1f ms, pair tables %.1f ms (bucketing %.1f, tables %.1f, merge %.1f); %.1f ms since the scan began\n",
-                        part, n_parts, sv, s_end, n_seg, pool.size(), t_inflate, t_hop, t_extract, now() - t_mark, t_bucket - t_mark, t_tables - t_bucket, now() - t_tables, now() - t_begin);
-    if (timing) fprintf(stderr, "[isx_bam_scan]   inside 'inflate', summed over the threads: block decode + buffers %.1f ms, start guess + record walk %.1f ms (guess %.1f)\n",
-                        thr_inflate_us.load() / 1e3, thr_hop_us.load() / 1e3, thr_guess_us.load() / 1e3);
-    {
-        size_t bytes = 0;
-        for (const auto &v : B.seg_reads) bytes += v.size() * sizeof(ReadLite);
-        if (bytes <= isx_bam::KEEP_DEAD && B.dead_reads.empty()) B.dead_reads.swap(B.seg_reads);       // unmapped with the handle (see isx_bam::retired)
-        else pool.run((int)B.seg_reads.size(), [&](int k) { uvec<ReadLite>().swap(B.seg_reads[(size_t)k]); });
-        B.seg_reads.clear();
-    }
-    // names stay until the filter has run (set_r2m / priority reads / cross-scaffold filters)
+    return ISX_OK;
+}
+
+void print_scan_times(const Scan &X)
+{
+    fprintf(stderr, "[isx_bam_scan] share %d/%d: segments [%zu, %zu) of %zu, %d threads: inflate %.1f ms, record walk %.1f ms, field extraction %.1f ms, pair tables %.1f ms (bucketing %.1f, tables %.1f, merge %.1f); %.1f ms since the scan began\n",
+            X.part, X.n_parts, X.sv, X.s_end, X.n_seg, X.pool.size(), X.t_inflate, X.t_hop, X.t_extract, now_ms() - X.t_mark, X.t_bucket - X.t_mark, X.t_tables - X.t_bucket, now_ms() - X.t_tables, now_ms() - X.t_begin);
+    fprintf(stderr, "[isx_bam_scan]   inside 'inflate', summed over the threads: block decode + buffers %.1f ms, start guess + record walk %.1f ms (guess %.1f)\n",
+            X.thr_inflate_us.load() / 1e3, X.thr_hop_us.load() / 1e3, X.thr_guess_us.load() / 1e3);
+}
+
+// the per-read records go (the names stay until the filter has run: set_r2m / priority reads / cross-scaffold filters); the totals
+void finish_scan(Scan &X)
+{
+    isx_bam &B = X.B;
+    size_t bytes = 0;
+    for (const auto &v : B.seg_reads) bytes += v.size() * sizeof(ReadLite);
+    if (bytes <= isx_bam::KEEP_DEAD && B.dead_reads.empty()) B.dead_reads.swap(B.seg_reads);       // unmapped with the handle (see isx_bam::retired)
+    else X.pool.run((int)B.seg_reads.size(), [&](int k) { uvec<ReadLite>().swap(B.seg_reads[(size_t)k]); });
+    B.seg_reads.clear();
     B.totals = isx_bam_info{};
-    B.totals.n_refs = (int32_t)n_ref;
+    B.totals.n_refs = (int32_t)X.n_ref;
     B.totals.n_reads = (int64_t)B.n_reads;
-    if (n_parts > 1) { B.totals.n_reads = 0; for (int64_t r : B.ref_reads) B.totals.n_reads += r; }     // the share's own references
+    if (X.n_parts > 1) { B.totals.n_reads = 0; for (int64_t r : B.ref_reads) B.totals.n_reads += r; }     // the share's own references
     for (int64_t l : B.ref_len) B.totals.n_pos += l;
     B.scanned = true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isx_bam_scan(isx_bam *bam, isx_bam_info *info) { return isx_bam_scan_part(bam, 0, 1, info); }
+
+// Pass 1 over ONE of n_parts shares of the file (ranks of a multi-GPU run: each scans its share, not the whole file).
+// The share is a range of segments of equal compressed size, [s0, s1); the handle OWNS the references whose first read lies in
+// it: their pair tables are complete (the scan runs on past s1 until the reference that straddles it has ended), every other
+// reference looks empty to this handle.  A share that does not start the file begins two segments early: the chain check
+// (a segment's first record must be where the previous segment's walk ended) then holds for its own first segment exactly
+// as in a whole-file scan, and the last read before s0 tells whether the reference at s0 began earlier (then it belongs to the
+// previous share).  What is global -- the median insert of the read filter -- is the caller's to combine
+// (isx_bam_insert_sizes of every share -> isx_bam_filter(median_insert)).
+int isx_bam_scan_part(isx_bam *bam, int32_t part, int32_t n_parts, isx_bam_info *info)
+{
+    if (!bam || n_parts < 1 || part < 0 || part >= n_parts) { isx_set_error("isx_bam_scan: bad argument"); return ISX_ERR_ARG; }
+    isx_bam &B = *bam;
+    if (B.scanned) {
+        if (B.part != part || B.n_parts != n_parts) { isx_set_error("isx_bam_scan: this handle already scanned another share of the file"); return ISX_ERR_STATE; }
+        if (info) *info = B.totals;
+        return ISX_OK;
+    }
+    B.part = part; B.n_parts = n_parts;
+    const size_t n_seg = B.segs.size();
+    const size_t s0 = n_seg * (size_t)part / (size_t)n_parts, s1 = n_seg * ((size_t)part + 1) / (size_t)n_parts;
+    const size_t sv = s0 == s1 ? 0 : s0 >= 2 ? s0 - 2 : 0;                 // (more shares than segments: this one is empty)
+    Scan X{B, pool_of(B), part, n_parts, B.ref_name.size(), n_seg, s0, s1, sv, s0 == s1 ? 0 : n_seg, sv == 0, sv == 0, B.first_rec};
+    X.timing = getenv("ISX_BAM_TIMING") != nullptr;
+    X.t_begin = X.t_mark = now_ms();
+    X.errs.resize(n_seg);
+    B.seg_reads.assign(n_seg, {}); B.seg_names.assign(n_seg, {});
+    // pass 2 needs the same bytes again: keep a file's inflated segments when they are a small part of what the host has free
+    X.keep_inflated = B.total_inflated <= inflate_cache_limit();
+    if (X.keep_inflated) { B.seg_cache.assign(n_seg, {}); B.seg_cache_rec.assign(n_seg, {}); }
+    int rc;
+    if ((rc = scan_waves(X)) != ISX_OK) return rc;
+    std::vector<uint8_t> owned;
+    if ((rc = owned_refs(X, owned)) != ISX_OK) return rc;
+    std::vector<std::vector<TidRun>> seg_runs;
+    segment_runs(X, seg_runs);
+    std::vector<std::vector<Run>> runs;
+    if ((rc = reference_runs(X, seg_runs, owned, runs)) != ISX_OK) return rc;
+    PairParts T;
+    bucket_by_name_partition(X, runs, T);
+    X.t_bucket = now_ms();
+    if ((rc = build_pair_tables(X, T)) != ISX_OK) return rc;
+    X.t_tables = now_ms();
+    if ((rc = merge_pair_tables(X, T)) != ISX_OK) return rc;
+    if (X.timing) print_scan_times(X);
+    finish_scan(X);
     if (info) *info = B.totals;
     return ISX_OK;
 }
@@ -1741,39 +1844,31 @@ int isx_bam_filter(isx_bam *bam, const isx_bam_params *p, double median_insert, 
     else if (p->pairing_filter == 2) B.pairs_scan = B.pairs;
     isxenc::HostPool &pool = pool_of(B);
     const size_t n_pairs = B.pairs.size();
-    const int C = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n_pairs / 32768 + 1));
-    auto c_lo = [&](int c) { return n_pairs * (size_t)c / (size_t)C; };
+    const Slices sl(pool, n_pairs, 32768);
+    const int C = sl.nt;
     struct Tally { int64_t reads = 0, pairs = 0, single = 0, f_pairs = 0, f_single = 0, f_bases = 0, max_mm = 0; std::vector<int64_t> ins; };
     std::vector<Tally> tl((size_t)C);
     // paired_read_filter: scaffolds in header order, names in order of first appearance
-    if (p->pairing_filter == 0) {
+    if (p->pairing_filter == 0 || B.cross_set) {
+        // the unfiltered tallies; paired_only keeps pairs and priority reads, the other modes start from every entry
+        const bool pairs_only = p->pairing_filter == 0;
         pool.run(C, [&](int c) {
             Tally &t = tl[(size_t)c];
-            for (size_t i = c_lo(c); i < c_lo(c + 1); i++) {
+            for (size_t i = sl.lo(c); i < sl.lo(c + 1); i++) {
                 PairInfo &e = B.pairs[i];
                 e.pass = false; e.in_filter = false;
                 if (e.reads == 0 || absent(i)) continue;
                 t.reads += e.reads; t.pairs += e.reads == 2; t.single += e.reads == 1;
-                e.in_filter = e.reads == 2 || B.priority[i];
+                e.in_filter = !pairs_only || e.reads == 2 || B.priority[i];
             }
         });
         for (const Tally &t : tl) { T.unfiltered_reads += t.reads; T.unfiltered_pairs += t.pairs; T.unfiltered_singletons += t.single; }
-    } else if (B.cross_set) {
+    }
+    if (p->pairing_filter != 0 && B.cross_set) {
         // the cross-scaffold look-ups were resolved by the caller over ALL shares (isx_bam_set_cross_names): a name met k times
         // in header order is, for non_discordant, kept when k == 1 or it is a priority read, dropped from both scaffolds when
         // k == 2 and a KeyError of the reference when k > 2 (paired_read_filter :497-512); for all_reads every occurrence
         // carries the merged info the caller summed (_merge_info, :514-532)
-        pool.run(C, [&](int c) {
-            Tally &t = tl[(size_t)c];
-            for (size_t i = c_lo(c); i < c_lo(c + 1); i++) {
-                PairInfo &e = B.pairs[i];
-                e.pass = false; e.in_filter = false;
-                if (e.reads == 0 || absent(i)) continue;
-                t.reads += e.reads; t.pairs += e.reads == 2; t.single += e.reads == 1;
-                e.in_filter = true;
-            }
-        });
-        for (const Tally &t : tl) { T.unfiltered_reads += t.reads; T.unfiltered_pairs += t.pairs; T.unfiltered_singletons += t.single; }
         for (size_t j = 0; j < B.cross_idx.size(); j++) {
             const size_t i = (size_t)B.cross_idx[j];
             PairInfo &e = B.pairs[i];
@@ -1787,7 +1882,7 @@ int isx_bam_filter(isx_bam *bam, const isx_bam_params *p, double median_insert, 
                 e.insert = -2; e.start = -1; e.stop = -1;
             }
         }
-    } else {
+    } else if (p->pairing_filter != 0) {
         for (PairInfo &e : B.pairs) { e.pass = false; e.in_filter = false; }
         // names are looked up across scaffolds (pair2scaffold)
         std::unordered_map<std::string_view, uint32_t> seen;        // name -> index of the entry that holds it now
@@ -1829,7 +1924,7 @@ int isx_bam_filter(isx_bam *bam, const isx_bam_params *p, double median_insert, 
         pool.run(C, [&](int c) {
             std::vector<uint32_t> &h = hist[(size_t)c];
             h.assign((size_t)HB, 0);
-            for (size_t i = c_lo(c); i < c_lo(c + 1); i++) {
+            for (size_t i = sl.lo(c); i < sl.lo(c + 1); i++) {
                 const PairInfo &e = B.pairs[i];
                 if (!e.in_filter || e.reads != 2) continue;
                 if (e.insert >= 0 && e.insert < HB) h[(size_t)e.insert]++; else odd[(size_t)c] = 1;
@@ -1858,7 +1953,7 @@ int isx_bam_filter(isx_bam *bam, const isx_bam_params *p, double median_insert, 
             std::vector<std::vector<uint32_t>>().swap(hist);
             pool.run(C, [&](int c) {
                 std::vector<int64_t> &v = tl[(size_t)c].ins;
-                for (size_t i = c_lo(c); i < c_lo(c + 1); i++) { const PairInfo &e = B.pairs[i]; if (e.in_filter && e.reads == 2) v.push_back(e.insert); }
+                for (size_t i = sl.lo(c); i < sl.lo(c + 1); i++) { const PairInfo &e = B.pairs[i]; if (e.in_filter && e.reads == 2) v.push_back(e.insert); }
             });
             std::vector<int64_t> ins;
             size_t n_ins = 0;
@@ -1879,8 +1974,8 @@ int isx_bam_filter(isx_bam *bam, const isx_bam_params *p, double median_insert, 
     std::vector<std::vector<std::pair<size_t, int64_t>>> per_ref((size_t)C);       // (reference, pairs that passed) per piece
     pool.run(C, [&](int c) {
         Tally &tc = tl[(size_t)c];
-        size_t i = c_lo(c);
-        const size_t end = c_lo(c + 1);
+        size_t i = sl.lo(c);
+        const size_t end = sl.lo(c + 1);
         size_t t = (size_t)(std::upper_bound(B.ref_pair0.begin(), B.ref_pair0.end(), (uint64_t)i) - B.ref_pair0.begin()) - 1;
         while (i < end) {
             while (t + 1 < B.ref_pair0.size() && B.ref_pair0[t + 1] <= i) t++;
@@ -2085,8 +2180,7 @@ int isx_bam_read_report(const isx_bam *bam, isx_read_report_row *rows, int32_t c
     std::vector<isx_read_report_row> part(piece_lo.size(), zero);
     isxenc::HostPool &pool = pool_of(const_cast<isx_bam &>(B));
     const bool timing = getenv("ISX_BAM_TIMING") != nullptr;       // tuning aid: stage times on stderr (no effect on results)
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
+    const double t_begin = now_ms();
     pool.run((int)piece_lo.size(), [&](int k) {
         isx_read_report_row &r = part[(size_t)k];
         const uint64_t hi = std::min<uint64_t>(piece_lo[(size_t)k] + REPORT_BLOCK, B.ref_pair0[(size_t)piece_ref[(size_t)k] + 1]);
@@ -2109,7 +2203,7 @@ int isx_bam_read_report(const isx_bam *bam, isx_read_report_row *rows, int32_t c
             r.sum_pid += pid;
         }
     });
-    const double t_sweep = now();
+    const double t_sweep = now_ms();
     pool.run((int)n_ref, [&](int ti) {
         const size_t t = (size_t)ti;
         isx_read_report_row r = zero;
@@ -2138,7 +2232,7 @@ int isx_bam_read_report(const isx_bam *bam, isx_read_report_row *rows, int32_t c
         }
         rows[t] = r;
     });
-    if (timing) fprintf(stderr, "isx_bam_read_report: sweep %.2f ms (%zu pieces), per-reference sums + medians %.2f ms\n", t_sweep - t_begin, piece_lo.size(), now() - t_sweep);
+    if (timing) fprintf(stderr, "isx_bam_read_report: sweep %.2f ms (%zu pieces), per-reference sums + medians %.2f ms\n", t_sweep - t_begin, piece_lo.size(), now_ms() - t_sweep);
     return ISX_OK;
 }
 
@@ -2201,30 +2295,40 @@ struct BamBatch {
     std::vector<int64_t> split_bounds;
     std::vector<int32_t> split_ref;
 
+    // The aligned-run walk: f(ref, q, j0, j1) for every M / = / X run of read r -- the run starts at reference position ref and query
+    // offset q; its columns [j0, j1) are the ones that are piled up: the reference's pileups are truncated to [0, scaffold length)
+    // (profile_utilities.py:150-153) and, for a one-reference batch, to the region.  j0 >= j1: nothing of the run is left.
+    template <class F>
+    void aligned_runs(const Read &r, F &&f) const
+    {
+        const int64_t ref_len = B->ref_len[(size_t)r.tid];
+        const uint32_t *cig = S.cigars.data() + r.cigar_off;
+        int64_t ref = r.pos, q = 0;
+        for (uint32_t k = 0; k < r.n_cigar; k++) {
+            const int eats = OP_EATS[cig[k] & 15];
+            const int64_t n = cig[k] >> 4;
+            if (eats == EATS_BOTH) {
+                int64_t j0 = std::max<int64_t>(0, -ref), j1 = std::min<int64_t>(n, ref_len - ref);
+                if (reg_hi >= 0) { j0 = std::max<int64_t>(j0, reg_lo - ref); j1 = std::min<int64_t>(j1, reg_hi - ref); }
+                f(ref, q, j0, j1);
+            }
+            if (eats & EATS_Q) q += n;
+            if (eats & EATS_R) ref += n;
+        }
+    }
+
     // how many observations read ri contributes (bases of M/=/X blocks inside the scaffold / region with quality >= minq)
     uint64_t count_read(size_t ri) const
     {
         const Read &r = S.reads[ri];
-        const int64_t ref_len = B->ref_len[(size_t)r.tid];
         const uint8_t *ql = r.qual;
         const uint8_t mq = minq;
-        int64_t ref = r.pos, q = 0;
         uint64_t n_out = 0;
-        for (uint32_t k = 0; k < r.n_cigar; k++) {
-            const uint32_t c = S.cigars[r.cigar_off + (uint64_t)k];
-            const int op = c & 15;
-            const int64_t n = c >> 4;
-            if (op == CM || op == CEQ || op == CX) {
-                // the reference's pileups are truncated to [0, scaffold length) (profile_utilities.py:150-153)
-                int64_t j0 = std::max<int64_t>(0, -ref), j1 = std::min<int64_t>(n, ref_len - ref);
-                if (reg_hi >= 0) { j0 = std::max<int64_t>(j0, reg_lo - ref); j1 = std::min<int64_t>(j1, reg_hi - ref); }
-                uint32_t m = 0;
-                for (int64_t j = j0; j < j1; j++) m += ql[q + j] >= mq;
-                n_out += m;
-                q += n; ref += n;
-            } else if (op == CI || op == CS) q += n;
-            else if (op == CD || op == CN) ref += n;
-        }
+        aligned_runs(r, [&](int64_t, int64_t q, int64_t j0, int64_t j1) {
+            uint32_t m = 0;
+            for (int64_t j = j0; j < j1; j++) m += ql[q + j] >= mq;
+            n_out += m;
+        });
         return n_out;
     }
 
@@ -2236,29 +2340,18 @@ struct BamBatch {
         const PairInfo &pi = B->pairs[r.pair_idx];
         const uint64_t hi = (uint64_t)(prm.skip_mm ? 0 : (uint16_t)B->level_of(pi.mm)) << 32;
         const int64_t base_off = boff[(size_t)r.tid];
-        const int64_t ref_len = B->ref_len[(size_t)r.tid];
         const uint8_t *ql = r.qual, *sq = r.seq;
         const uint8_t mq = minq;
         uint64_t *o64 = reinterpret_cast<uint64_t *>(out);
-        int64_t ref = r.pos, q = 0;
         uint32_t n_out = 0;
-        for (uint32_t k = 0; k < r.n_cigar; k++) {
-            const uint32_t c = S.cigars[r.cigar_off + (uint64_t)k];
-            const int op = c & 15;
-            const int64_t n = c >> 4;
-            if (op == CM || op == CEQ || op == CX) {
-                int64_t j0 = std::max<int64_t>(0, -ref), j1 = std::min<int64_t>(n, ref_len - ref);
-                if (reg_hi >= 0) { j0 = std::max<int64_t>(j0, reg_lo - ref); j1 = std::min<int64_t>(j1, reg_hi - ref); }
-                const uint64_t g0 = (uint64_t)(uint32_t)(base_off + ref);
-                for (int64_t j = j0; j < j1; j++) {
-                    const int64_t i = q + j;
-                    o64[n_out] = (g0 + (uint64_t)j) | hi | ((uint64_t)CODE2IDX[nib(sq, i)] << 48);    // gpos | mm << 32 | base << 48
-                    n_out += ql[i] >= mq;
-                }
-                q += n; ref += n;
-            } else if (op == CI || op == CS) q += n;
-            else if (op == CD || op == CN) ref += n;
-        }
+        aligned_runs(r, [&](int64_t ref, int64_t q, int64_t j0, int64_t j1) {
+            const uint64_t g0 = (uint64_t)(uint32_t)(base_off + ref);
+            for (int64_t j = j0; j < j1; j++) {
+                const int64_t i = q + j;
+                o64[n_out] = (g0 + (uint64_t)j) | hi | ((uint64_t)CODE2IDX[nib(sq, i)] << 48);    // gpos | mm << 32 | base << 48
+                n_out += ql[i] >= mq;
+            }
+        });
         return n_out;
     }
 
@@ -2267,76 +2360,35 @@ struct BamBatch {
     uvec<uint32_t> seg_gpos;                // [n_segs] flat start of every segment (the staging encoder's layout pass wants them up front)
     int64_t n_seg_bases = 0;                // columns covered by the segments (>= the observations)
 
-    // calls f(flat start, query offset, columns) for every segment of read ri: the M / = / X runs of its CIGAR, truncated to
-    // the scaffold / region like the reference's pileup (profile_utilities.py:150-153), cut every ISX_SEG_BASES columns
+    // calls f(flat start, query offset, columns) for every segment of read ri: its aligned runs, cut every ISX_SEG_BASES columns
     template <class F>
     void for_segments(size_t ri, F &&f) const
     {
         const Read &r = S.reads[ri];
         const int64_t base_off = boff[(size_t)r.tid];
-        const int64_t ref_len = B->ref_len[(size_t)r.tid];
-        int64_t ref = r.pos, q = 0;
-        for (uint32_t k = 0; k < r.n_cigar; k++) {
-            const uint32_t c = S.cigars[r.cigar_off + (uint64_t)k];
-            const int op = c & 15;
-            const int64_t n = c >> 4;
-            if (op == CM || op == CEQ || op == CX) {
-                int64_t j0 = std::max<int64_t>(0, -ref), j1 = std::min<int64_t>(n, ref_len - ref);
-                if (reg_hi >= 0) { j0 = std::max<int64_t>(j0, reg_lo - ref); j1 = std::min<int64_t>(j1, reg_hi - ref); }
-                for (int64_t c0 = j0; c0 < j1; c0 += ISX_SEG_BASES)
-                    f(base_off + ref + c0, q + c0, std::min<int64_t>(ISX_SEG_BASES, j1 - c0));
-                q += n; ref += n;
-            } else if (op == CI || op == CS) q += n;
-            else if (op == CD || op == CN) ref += n;
-        }
+        aligned_runs(r, [&](int64_t ref, int64_t q, int64_t j0, int64_t j1) {
+            for (int64_t c0 = j0; c0 < j1; c0 += ISX_SEG_BASES)
+                f(base_off + ref + c0, q + c0, std::min<int64_t>(ISX_SEG_BASES, j1 - c0));
+        });
     }
 
-    // segments [first, first + count) of the batch's stream (thread safe); pair may be NULL
-    void emit_segs(int64_t first, int64_t count, uint32_t *gpos, uint8_t *len, uint8_t *mm, uint32_t *pair, uint32_t *bases) const
+    // segments [first, first + count) of the batch's stream (thread safe): the range walk of both forms.  pack(read, query offset,
+    // columns, k) writes the columns of output segment k; mm / pair may be NULL; with_mm: the pairs' levels, at most level_cap
+    template <class Pack>
+    void emit_seg_range(int64_t first, int64_t count, bool with_mm, int32_t level_cap, uint32_t *gpos, uint8_t *len, uint8_t *mm, uint32_t *pair,
+                        Pack &&pack) const
     {
         size_t ri = (size_t)(std::upper_bound(seg_at.begin(), seg_at.end(), (uint64_t)first) - seg_at.begin()) - 1;
         int64_t skip = first - (int64_t)seg_at[ri], done = 0;
-        const bool fast = cpu_has_avx2_bmi2();
-        const uint8_t mq = minq;
-        alignas(32) uint8_t cd[192];
         for (; done < count; ri++) {
             if (seg_at[ri + 1] == seg_at[ri]) continue;
             const Read &r = S.reads[ri];
-            const uint8_t m = prm.skip_mm ? (uint8_t)0 : (uint8_t)std::min<int32_t>(std::min<int32_t>(255, B->mm_cap), (int32_t)pair_mm[(size_t)r.pair_idx - pair_mm_lo]);
+            const uint8_t m = with_mm ? (uint8_t)std::min<int32_t>(std::min<int32_t>(level_cap, B->mm_cap), (int32_t)pair_mm[(size_t)r.pair_idx - pair_mm_lo]) : (uint8_t)0;
             const uint32_t id = pid[ri];
             for_segments(ri, [&](int64_t g, int64_t q0, int64_t cols) {
                 if (skip > 0) { skip--; return; }
                 if (done >= count) return;
-                if (fast) { seg_codes_avx2(r.seq, r.qual, q0, (int)cols, mq, cd); seg_pack_bmi2(cd, (int)cols, bases + (size_t)done * ISX_SEG_WORDS); }
-                else { seg_codes_scalar(r.seq, r.qual, q0, (int)cols, mq, cd); seg_pack_scalar(cd, (int)cols, bases + (size_t)done * ISX_SEG_WORDS); }
-                gpos[done] = (uint32_t)g; len[done] = (uint8_t)cols; mm[done] = m;
-                if (pair) pair[done] = id;
-                done++;
-            });
-            skip = 0;
-        }
-    }
-
-    // the same segments as bit planes (isx_read_planes: one 64-byte line each); mm != NULL (mm profiling on): the pairs' levels too, and
-    // the non-ACGT bases that pass the filter are marked in the lines
-    void emit_planes(int64_t first, int64_t count, uint32_t *gpos, uint8_t *len, uint8_t *mm, uint32_t *pair, uint64_t *planes) const
-    {
-        size_t ri = (size_t)(std::upper_bound(seg_at.begin(), seg_at.end(), (uint64_t)first) - seg_at.begin()) - 1;
-        int64_t skip = first - (int64_t)seg_at[ri], done = 0;
-        const bool fast = cpu_has_avx512bw();
-        const uint8_t mq = minq;
-        for (; done < count; ri++) {
-            if (seg_at[ri + 1] == seg_at[ri]) continue;
-            const Read &r = S.reads[ri];
-            const uint32_t id = pid[ri];
-            const bool mark = mm != nullptr && !prm.skip_mm;
-            const uint8_t m = mark ? (uint8_t)std::min<int32_t>(std::min<int32_t>(127, B->mm_cap), (int32_t)pair_mm[(size_t)r.pair_idx - pair_mm_lo]) : (uint8_t)0;
-            for_segments(ri, [&](int64_t g, int64_t q0, int64_t cols) {
-                if (skip > 0) { skip--; return; }
-                if (done >= count) return;
-                uint64_t *P = planes + (size_t)done * ISX_PLANE_WORDS;
-                if (fast) seg_planes_avx512(r.seq, r.qual, q0, (int)cols, mq, P, mark);
-                else seg_planes_scalar(r.seq, r.qual, q0, (int)cols, mq, P, mark);
+                pack(r, q0, (int)cols, done);
                 gpos[done] = (uint32_t)g; len[done] = (uint8_t)cols;
                 if (mm) mm[done] = m;
                 if (pair) pair[done] = id;
@@ -2344,6 +2396,31 @@ struct BamBatch {
             });
             skip = 0;
         }
+    }
+
+    // ... as 3-bit codes, ten a word
+    void emit_segs(int64_t first, int64_t count, uint32_t *gpos, uint8_t *len, uint8_t *mm, uint32_t *pair, uint32_t *bases) const
+    {
+        const bool fast = cpu_has_avx2_bmi2();
+        const uint8_t mq = minq;
+        alignas(32) uint8_t cd[192];
+        emit_seg_range(first, count, !prm.skip_mm, 255, gpos, len, mm, pair, [&](const Read &r, int64_t q0, int cols, int64_t k) {
+            if (fast) { seg_codes_avx2(r.seq, r.qual, q0, cols, mq, cd); seg_pack_bmi2(cd, cols, bases + (size_t)k * ISX_SEG_WORDS); }
+            else { seg_codes_scalar(r.seq, r.qual, q0, cols, mq, cd); seg_pack_scalar(cd, cols, bases + (size_t)k * ISX_SEG_WORDS); }
+        });
+    }
+
+    // ... as bit planes (isx_read_planes: one 64-byte line each); mm != NULL (mm profiling on): the pairs' levels too, and the non-ACGT
+    // bases that pass the filter are marked in the lines
+    void emit_planes(int64_t first, int64_t count, uint32_t *gpos, uint8_t *len, uint8_t *mm, uint32_t *pair, uint64_t *planes) const
+    {
+        const bool fast = cpu_has_avx512bw(), mark = mm != nullptr && !prm.skip_mm;
+        const uint8_t mq = minq;
+        emit_seg_range(first, count, mark, 127, gpos, len, mm, pair, [&](const Read &r, int64_t q0, int cols, int64_t k) {
+            uint64_t *P = planes + (size_t)k * ISX_PLANE_WORDS;
+            if (fast) seg_planes_avx512(r.seq, r.qual, q0, cols, mq, P, mark);
+            else seg_planes_scalar(r.seq, r.qual, q0, cols, mq, P, mark);
+        });
     }
 
     // observations [first, first + count) of the batch's stream (thread safe)
@@ -2375,62 +2452,66 @@ struct BamBatch {
     int64_t n_obs() const { return (int64_t)out_at.back(); }
 };
 
-int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs, int32_t n_refs, BamBatch **out, int64_t reg_lo, int64_t reg_hi,
-                      bool as_segments)
+// ---- bam_batch_prepare: a driver over the stages below.  What they share besides the batch itself: ----
+struct BatchPlan {
+    isx_bam &B;
+    BamBatch &Q;
+    isxenc::HostPool &pool;
+    const isx_bam_params *p;
+    const int32_t *refs;
+    int32_t n_refs;
+    bool region, as_segments;
+    std::vector<uint32_t> seg_list;         // the file's segments that hold reads of the batch
+};
+
+// argument checks; the batch's flat space (its references laid end to end, file order), the region, the segments to load
+static int plan_batch(BatchPlan &A, int64_t reg_lo, int64_t reg_hi)
 {
-    *out = nullptr;
-    isx_bam &B = *bam;
-    if (!B.scanned || !B.filtered) { isx_set_error("isx_bam_expand_refs: scan and filter first"); return ISX_ERR_STATE; }
+    isx_bam &B = A.B;
+    BamBatch &Q = A.Q;
     const size_t n_ref_all = B.ref_name.size();
-    isxenc::HostPool &pool = pool_of(B);
-    const bool timing = getenv("ISX_BAM_TIMING") != nullptr;       // tuning aid: stage times on stderr (no effect on results)
-    auto t_last = std::chrono::steady_clock::now();
-    auto stage = [&](const char *what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[isx_bam_expand_refs] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-    std::unique_ptr<BamBatch> Q(new BamBatch());
-    Q->B = bam; Q->prm = *p;
-    Q->minq = (uint8_t)std::min(255, std::max(0, p->min_base_quality));
-    // flat space of the batch: its references laid end to end (file order)
-    std::vector<int64_t> &boff = Q->boff;
-    boff.assign(n_ref_all, -1);
+    Q.boff.assign(n_ref_all, -1);
     int64_t n_pos = 0;
     std::vector<uint8_t> seg_wanted(B.segs.size(), 0);
-    for (int32_t i = 0; i < n_refs; i++) {
-        const int32_t t = refs[i];
-        if (t < 0 || (size_t)t >= n_ref_all || (i > 0 && t <= refs[i - 1])) { isx_set_error("isx_bam_expand_refs: reference ids must be valid and ascending (file order: the stream stays position-clustered)"); return ISX_ERR_ARG; }
-        boff[(size_t)t] = n_pos;
+    for (int32_t i = 0; i < A.n_refs; i++) {
+        const int32_t t = A.refs[i];
+        if (t < 0 || (size_t)t >= n_ref_all || (i > 0 && t <= A.refs[i - 1])) { isx_set_error("isx_bam_expand_refs: reference ids must be valid and ascending (file order: the stream stays position-clustered)"); return ISX_ERR_ARG; }
+        Q.boff[(size_t)t] = n_pos;
         n_pos += B.ref_len[(size_t)t];
         if (B.ref_reads[(size_t)t])
             for (uint32_t s = B.ref_seg0[(size_t)t]; s <= B.ref_seg1[(size_t)t]; s++) seg_wanted[s] = 1;
     }
     if (n_pos >= (int64_t)0xFFFF0000ll) { isx_set_error("isx_bam_expand_refs: the batch's flat space must be < 2^32 - 65536 positions"); return ISX_ERR_ARG; }
-    Q->n_pos = n_pos;
-    const bool region = reg_hi >= 0;
-    if (region) {
-        if (n_refs != 1 || reg_lo < 0 || reg_hi <= reg_lo) { isx_set_error("isx_bam_expand_region: one reference and 0 <= start < stop"); return ISX_ERR_ARG; }
-        Q->reg_lo = reg_lo; Q->reg_hi = std::min<int64_t>(reg_hi, B.ref_len[(size_t)refs[0]]);
+    Q.n_pos = n_pos;
+    if (A.region) {
+        if (A.n_refs != 1 || reg_lo < 0 || reg_hi <= reg_lo) { isx_set_error("isx_bam_expand_region: one reference and 0 <= start < stop"); return ISX_ERR_ARG; }
+        Q.reg_lo = reg_lo; Q.reg_hi = std::min<int64_t>(reg_hi, B.ref_len[(size_t)A.refs[0]]);
         // the file is sorted: segments whose records all start at or after the region's end, or so far before its start that
         // no read reaches it, cannot contribute
         for (uint32_t s = 0; s < B.segs.size(); s++) {
             if (!seg_wanted[s]) continue;
             const Segment &sg = B.segs[s];
-            if (sg.tid_first == refs[0] && sg.pos_first >= Q->reg_hi) seg_wanted[s] = 0;
-            if (sg.tid_last == refs[0] && (int64_t)sg.pos_last + B.max_span <= Q->reg_lo) seg_wanted[s] = 0;
+            if (sg.tid_first == A.refs[0] && sg.pos_first >= Q.reg_hi) seg_wanted[s] = 0;
+            if (sg.tid_last == A.refs[0] && (int64_t)sg.pos_last + B.max_span <= Q.reg_lo) seg_wanted[s] = 0;
         }
     }
-    std::vector<uint32_t> seg_list;
-    for (uint32_t s = 0; s < B.segs.size(); s++) if (seg_wanted[s]) seg_list.push_back(s);
+    for (uint32_t s = 0; s < B.segs.size(); s++) if (seg_wanted[s]) A.seg_list.push_back(s);
+    return ISX_OK;
+}
 
-    // ---- load the batch's reads: inflate + walk + count per segment, then fill ----
+// the batch's reads: inflate + walk + count per segment, then fill Q.S (reads, CIGARs; the batch takes the inflated segments over)
+static int load_reads(BatchPlan &A)
+{
+    isx_bam &B = A.B;
+    BamBatch &Q = A.Q;
+    const std::vector<uint32_t> &seg_list = A.seg_list;
+    const std::vector<int64_t> &boff = Q.boff;
+    const size_t n_ref_all = B.ref_name.size();
     struct SegWork { SegBuf buf; std::vector<uint64_t> rec; const uint8_t *data = nullptr; const std::vector<uint64_t> *recp = nullptr;
                      std::vector<uint32_t> keep; uint64_t n_cig = 0, n_seq = 0; std::string err; };
     std::vector<SegWork> sw(seg_list.size());
     std::atomic<int> rc_any{0};
-    pool.run((int)seg_list.size(), [&](int k) {
+    A.pool.run((int)seg_list.size(), [&](int k) {
         const Segment &s = B.segs[seg_list[(size_t)k]];
         SegWork &w = sw[(size_t)k];
         const bool cached = !B.seg_cache.empty() && !B.seg_cache[seg_list[(size_t)k]].empty();
@@ -2448,9 +2529,9 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
             const int32_t tid = rd32(q + 4);
             if (tid < 0 || (size_t)tid >= n_ref_all || boff[(size_t)tid] < 0) continue;
             if (rd16(q + 18) & DEF_MASK) continue;                     // htslib's pileup never sees these
-            if (region) {                                               // the fetch of a region only yields reads that overlap it
+            if (A.region) {                                             // the fetch of a region only yields reads that overlap it
                 const int32_t pos = rd32(q + 8);
-                if (pos >= Q->reg_hi || (int64_t)pos + B.max_span <= Q->reg_lo) continue;
+                if (pos >= Q.reg_hi || (int64_t)pos + B.max_span <= Q.reg_lo) continue;
             }
             w.keep.push_back(i);
             if (rd16(q + 16) == 2) {                                    // maybe the placeholder of a CIGAR kept in the CG tag
@@ -2461,14 +2542,14 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
             w.n_seq += (uint64_t)std::max(rd32(q + 20), 0);
         }
     });
-    if (rc_any.load()) { for (auto &w : sw) if (!w.err.empty()) { isx_set_error(w.err); break; } return rc_any.load(); }
+    if (rc_any.load()) return hand_back_error(rc_any.load(), sw);
     std::vector<uint64_t> r_at(sw.size() + 1, 0), c_at(sw.size() + 1, 0), s_at(sw.size() + 1, 0);
     for (size_t k = 0; k < sw.size(); k++) { r_at[k + 1] = r_at[k] + sw[k].keep.size(); c_at[k + 1] = c_at[k] + sw[k].n_cig; s_at[k + 1] = s_at[k] + sw[k].n_seq; }
-    Batch &S = Q->S;
+    Batch &S = Q.S;
     S.reads.resize((size_t)r_at.back());
     S.cigars.resize((size_t)c_at.back());
     S.seg_data.resize(sw.size());
-    pool.run((int)sw.size(), [&](int k) {
+    A.pool.run((int)sw.size(), [&](int k) {
         const Segment &s = B.segs[seg_list[(size_t)k]];
         SegWork &w = sw[(size_t)k];
         uint64_t ci = c_at[(size_t)k];
@@ -2478,7 +2559,7 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
         // for it again; if somebody does it is inflated anew), copied otherwise.
         if (w.buf.data.empty()) {
             uvec<uint8_t> &kept = B.seg_cache[seg_list[(size_t)k]];
-            bool others = region;
+            bool others = A.region;
             for (int32_t t = std::max(s.tid_first, 0); t <= s.tid_last && !others; t++)
                 if (B.ref_reads[(size_t)t] > 0 && boff[(size_t)t] < 0) others = true;
             if (others) w.buf.data = kept;
@@ -2500,208 +2581,235 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
             ci += r.n_cigar;
         }
     });
-    if (rc_any.load()) { for (auto &w : sw) if (!w.err.empty()) { isx_set_error(w.err); break; } return rc_any.load(); }
-    sw.clear();
-    stage("load reads");
+    return rc_any.load() ? hand_back_error(rc_any.load(), sw) : ISX_OK;
+}
 
-    // ---- max_depth = 100000 of the pileup call (profile_utilities.py:150, polymorpher.py:290) as htslib 1.9 applies it
-    //      (bam_plp_push, sam.c): a read that starts exactly at the column the iterator stands on -- i.e. any read but the first
-    //      of a run of equal starts -- is not pushed while the buffer's node pool holds more than max_depth nodes (the buffered
-    //      reads, whose end lies at or beyond that start, + the list's sentinel).  Dropped reads take no part in the overlap
-    //      resolution and reach no column.  Only a position with >= 100000 reads over it can drop anything: a parallel screen
-    //      (reads starting within the longest read span of each start) decides whether the serial replay runs at all.
-    //      PARITY UNPINNED (no reference fixture is that deep; restated from the htslib-1.9 source; the tests hold a second, pure-Python restatement,
-    //      which replays every split literally: its own reads, its own buffer, its own columns).
-    {
-        constexpr int64_t MAX_DEPTH = 100000;
-        const size_t n_all = S.reads.size();
-        if (n_all > (size_t)MAX_DEPTH) {
-            const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n_all / 65536 + 1));
-            std::vector<int64_t> span_max((size_t)nt, 0);
-            pool.run(nt, [&](int t) {
-                int64_t m = 0;
-                for (size_t i = n_all * (size_t)t / (size_t)nt; i < n_all * (size_t)(t + 1) / (size_t)nt; i++) m = std::max(m, S.reads[i].ref_end - (int64_t)S.reads[i].pos);
-                span_max[(size_t)t] = m;
-            });
-            const int64_t L = std::max<int64_t>(1, *std::max_element(span_max.begin(), span_max.end()));
-            std::atomic<int> deep{0};
-            pool.run(nt, [&](int t) {           // reads of the same reference that start in (pos - L, pos]: an upper bound of the buffer there
-                const size_t a = n_all * (size_t)t / (size_t)nt, e = n_all * (size_t)(t + 1) / (size_t)nt;
-                size_t lo = a;
-                while (lo > 0 && S.reads[lo - 1].tid == S.reads[a].tid && (int64_t)S.reads[lo - 1].pos > (int64_t)S.reads[a].pos - L) lo--;
-                for (size_t i = a; i < e; i++) {
-                    while (S.reads[lo].tid != S.reads[i].tid || (int64_t)S.reads[lo].pos <= (int64_t)S.reads[i].pos - L) lo++;
-                    if ((int64_t)(i - lo + 1) >= MAX_DEPTH) { deep.store(1); return; }
-                }
-            });
-            if (deep.load()) {
-                // Round 6: the replay is restarted PER SPLIT, as the reference's iterator is (profile_utilities.py:150-153: one
-                // samfile.pileup(..., max_depth=100000, start=start, stop=end+1) per split, fasta.py:56-73 iterate_splits): a split's
-                // iterator is fed the reads that overlap [start, end] (pos <= end, bam_endpos > start) and starts with an empty buffer.
-                // A read that overlaps two splits is replayed in both and can be dropped in one and taken in the other (a pile
-                // within a read's length before a split bound: the buffer of the later split's iterator never saw the reads that
-                // end before the bound).  Such a read keeps its place in the stream; its CIGAR is rewritten so that it covers no
-                // column of the splits that dropped it -- M/=/X there become I + N, D becomes N -- and everything downstream
-                // (overlap resolution, expansion) sees a read that is absent exactly there.  Dropped everywhere: removed as before.
-                const int64_t WL = p->window_length > 0 ? p->window_length : 10000;
-                std::priority_queue<int64_t, std::vector<int64_t>, std::greater<int64_t>> ends;
-                std::vector<uint16_t> n_seen(n_all, 0), n_drop(n_all, 0);
-                std::vector<std::pair<uint32_t, int32_t>> drops;        // (read, split ordinal on its reference)
-                size_t i0 = 0;
-                while (i0 < n_all) {
-                    const int32_t tid = S.reads[i0].tid;
-                    size_t i1 = i0;
-                    while (i1 < n_all && S.reads[i1].tid == tid) i1++;
-                    const int64_t sLen = tid >= 0 ? B.ref_len[(size_t)tid] : 0;
-                    if (sLen > 0) {
-                        const int64_t nC = sLen / WL + 1, chunk = (int64_t)((double)sLen / (double)nC);
-                        size_t lo = i0;
-                        for (int64_t c = 0; c < nC; c++) {
-                            const int64_t s0 = c * chunk, e0 = c + 1 == nC ? sLen - 1 : (c + 1) * chunk - 1;
-                            while (lo < i1 && (int64_t)S.reads[lo].pos + L <= s0) lo++;      // (cannot reach the split: ref_end <= pos + L)
-                            ends = decltype(ends)();
-                            int32_t prev_pos = -1;
-                            for (size_t i = lo; i < i1 && (int64_t)S.reads[i].pos <= e0; i++) {
-                                const Read &r = S.reads[i];
-                                if (std::max<int64_t>(r.ref_end, (int64_t)r.pos + 1) <= s0) continue;       // not fetched for this split
-                                while (!ends.empty() && ends.top() < (int64_t)r.pos) ends.pop();
-                                if (n_seen[i] < 0xFFFF) n_seen[i]++;
-                                if (prev_pos == r.pos && (int64_t)ends.size() + 1 > MAX_DEPTH) { if (n_drop[i] < 0xFFFF) n_drop[i]++; drops.emplace_back((uint32_t)i, (int32_t)c); continue; }
-                                prev_pos = r.pos;
-                                ends.push(r.ref_end);
-                            }
-                        }
-                    }
-                    i0 = i1;
-                }
-                // what the drops mean for each read
-                std::vector<uint32_t> extra;                            // rewritten CIGARs, appended to S.cigars below
-                const size_t old_n = S.cigars.size();
-                std::sort(drops.begin(), drops.end());
-                for (size_t d = 0; d < drops.size();) {
-                    const uint32_t ri = drops[d].first;
-                    size_t d1 = d;
-                    while (d1 < drops.size() && drops[d1].first == ri) d1++;
-                    Read &r = S.reads[ri];
-                    if (n_drop[ri] >= n_seen[ri]) { r.pair_idx = 0xFFFFFFFFu; r.flag |= FUNMAP; d = d1; continue; }     // no iterator took it
-                    const int64_t sLen = B.ref_len[(size_t)r.tid];
-                    const int64_t nC = sLen / WL + 1, chunk = (int64_t)((double)sLen / (double)nC);
-                    auto split_of = [&](int64_t rp) { return chunk > 0 ? std::min<int64_t>(rp / chunk, nC - 1) : 0; };
-                    auto split_end = [&](int64_t c) { return c + 1 == nC ? sLen - 1 : (c + 1) * chunk - 1; };
-                    auto is_dropped = [&](int64_t c) { for (size_t k = d; k < d1; k++) if (drops[k].second == (int32_t)c) return true; return false; };
-                    const uint64_t new_off = (uint64_t)old_n + extra.size();
-                    int64_t rp = r.pos;
-                    for (uint32_t k = 0; k < r.n_cigar; k++) {
-                        const uint32_t cg = S.cigars[r.cigar_off + (uint64_t)k];
-                        const uint32_t op = cg & 15u;
-                        int64_t n = (int64_t)(cg >> 4);
-                        const bool m_like = op == CM || op == CEQ || op == CX, d_like = op == CD || op == CN;
-                        if (!m_like && !d_like) { extra.push_back(cg); continue; }           // consumes no reference: as it is
-                        while (n > 0) {             // the operation cut at the split bounds it crosses
-                            const int64_t c = rp >= 0 && rp < sLen ? split_of(rp) : -1;
-                            const int64_t run = c < 0 ? n : std::min<int64_t>(n, split_end(c) - rp + 1);
-                            if (c >= 0 && is_dropped(c)) {
-                                if (m_like) extra.push_back((uint32_t)(run << 4) | CI);
-                                extra.push_back((uint32_t)(run << 4) | CN);
-                            } else extra.push_back((uint32_t)(run << 4) | op);
-                            rp += run; n -= run;
-                        }
-                    }
-                    r.cigar_off = new_off;
-                    r.n_cigar = (uint32_t)((uint64_t)old_n + extra.size() - new_off);
-                    d = d1;
-                }
-                if (!extra.empty()) {
-                    RawBuf<uint32_t> nb;
-                    nb.resize(old_n + extra.size());
-                    memcpy(nb.p, S.cigars.p, old_n * sizeof(uint32_t));
-                    memcpy(nb.p + old_n, extra.data(), extra.size() * sizeof(uint32_t));
-                    std::swap(nb.p, S.cigars.p);
-                    std::swap(nb.n, S.cigars.n);
-                }
+// ---- max_depth = 100000 of the pileup call (profile_utilities.py:150, polymorpher.py:290) as htslib 1.9 applies it
+//      (bam_plp_push, sam.c): a read that starts exactly at the column the iterator stands on -- i.e. any read but the first
+//      of a run of equal starts -- is not pushed while the buffer's node pool holds more than max_depth nodes (the buffered
+//      reads, whose end lies at or beyond that start, + the list's sentinel).  Dropped reads take no part in the overlap
+//      resolution and reach no column.  Only a position with >= 100000 reads over it can drop anything: a parallel screen
+//      (reads starting within the longest read span of each start) decides whether the serial replay runs at all.
+//      PARITY UNPINNED (no reference fixture is that deep; restated from the htslib-1.9 source; the tests hold a second, pure-Python restatement,
+//      which replays every split literally: its own reads, its own buffer, its own columns).
+constexpr int64_t MAX_DEPTH = 100000;
+
+// the screen: the longest reference span of a read of the batch (>= 1) when some column may hold MAX_DEPTH reads, 0 when none can
+static int64_t max_depth_screen(BatchPlan &A)
+{
+    const Batch &S = A.Q.S;
+    const Slices sl(A.pool, S.reads.size(), 65536);
+    std::vector<int64_t> span_max((size_t)sl.nt, 0);
+    A.pool.run(sl.nt, [&](int t) {
+        int64_t m = 0;
+        for (size_t i = sl.lo(t); i < sl.lo(t + 1); i++) m = std::max(m, S.reads[i].ref_end - (int64_t)S.reads[i].pos);
+        span_max[(size_t)t] = m;
+    });
+    const int64_t L = std::max<int64_t>(1, *std::max_element(span_max.begin(), span_max.end()));
+    std::atomic<int> deep{0};
+    A.pool.run(sl.nt, [&](int t) {             // reads of the same reference that start in (pos - L, pos]: an upper bound of the buffer there
+        const size_t a = sl.lo(t), e = sl.lo(t + 1);
+        size_t lo = a;
+        while (lo > 0 && S.reads[lo - 1].tid == S.reads[a].tid && (int64_t)S.reads[lo - 1].pos > (int64_t)S.reads[a].pos - L) lo--;
+        for (size_t i = a; i < e; i++) {
+            while (S.reads[lo].tid != S.reads[i].tid || (int64_t)S.reads[lo].pos <= (int64_t)S.reads[i].pos - L) lo++;
+            if ((int64_t)(i - lo + 1) >= MAX_DEPTH) { deep.store(1); return; }
+        }
+    });
+    return deep.load() ? L : 0;
+}
+
+struct DepthDrops {
+    std::vector<uint16_t> n_seen, n_drop;                   // per read: the splits whose iterator was fed it / did not take it
+    std::vector<std::pair<uint32_t, int32_t>> drops;        // (read, split ordinal on its reference)
+};
+
+// Round 6: the replay is restarted PER SPLIT, as the reference's iterator is (profile_utilities.py:150-153: one
+// samfile.pileup(..., max_depth=100000, start=start, stop=end+1) per split, fasta.py:56-73 iterate_splits): a split's
+// iterator is fed the reads that overlap [start, end] (pos <= end, bam_endpos > start) and starts with an empty buffer.
+// A read that overlaps two splits is replayed in both and can be dropped in one and taken in the other (a pile
+// within a read's length before a split bound: the buffer of the later split's iterator never saw the reads that
+// end before the bound).
+static void max_depth_replay(const isx_bam &B, const Batch &S, int64_t L, int64_t WL, DepthDrops &D)
+{
+    const size_t n_all = S.reads.size();
+    std::priority_queue<int64_t, std::vector<int64_t>, std::greater<int64_t>> ends;
+    D.n_seen.assign(n_all, 0); D.n_drop.assign(n_all, 0);
+    for (size_t i0 = 0, i1; i0 < n_all; i0 = i1) {
+        const int32_t tid = S.reads[i0].tid;
+        for (i1 = i0; i1 < n_all && S.reads[i1].tid == tid;) i1++;
+        const int64_t sLen = tid >= 0 ? B.ref_len[(size_t)tid] : 0;
+        if (sLen <= 0) continue;
+        const Splits sp(sLen, WL);
+        size_t lo = i0;
+        for (int64_t c = 0; c < sp.n; c++) {
+            const int64_t s0 = sp.start(c), e0 = sp.end(c);
+            while (lo < i1 && (int64_t)S.reads[lo].pos + L <= s0) lo++;      // (cannot reach the split: ref_end <= pos + L)
+            ends = decltype(ends)();
+            int32_t prev_pos = -1;
+            for (size_t i = lo; i < i1 && (int64_t)S.reads[i].pos <= e0; i++) {
+                const Read &r = S.reads[i];
+                if (std::max<int64_t>(r.ref_end, (int64_t)r.pos + 1) <= s0) continue;       // not fetched for this split
+                while (!ends.empty() && ends.top() < (int64_t)r.pos) ends.pop();
+                if (D.n_seen[i] < 0xFFFF) D.n_seen[i]++;
+                if (prev_pos == r.pos && (int64_t)ends.size() + 1 > MAX_DEPTH) { if (D.n_drop[i] < 0xFFFF) D.n_drop[i]++; D.drops.emplace_back((uint32_t)i, (int32_t)c); continue; }
+                prev_pos = r.pos;
+                ends.push(r.ref_end);
             }
-            stage("max_depth");
         }
     }
+}
 
-    // ---- overlap_push in file order (htslib-1.9 rule |isize| < 2*l_qseq), partitioned by pair: a pair's two reads
-    //      only ever touch each other's qualities ----
-    const size_t n_reads = S.reads.size();
-    {
-        // candidates only (both mates mapped, proper pair, |isize| < 2 * l_qseq), bucketed by pair so that a task touches its
-        // own reads and not every read of the batch
-        const int P = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n_reads / 16384 + 1));
-        std::vector<uint32_t> order;
-        std::vector<size_t> start;
-        if (n_reads >= 0xFFFFFFFFull) { isx_set_error("isx_bam_expand_refs: more than 2^32 reads in one batch"); return ISX_ERR_ARG; }
-        bucket_indices(pool, n_reads, P, [&](size_t ri) -> int {
-            const Read &r = S.reads[ri];
-            if (r.pair_idx == 0xFFFFFFFFu || (r.flag & FMUNMAP) || !(r.flag & FPROPER)) return -1;
-            if (std::abs((int64_t)r.isize) >= 2 * (int64_t)r.l_seq) return -1;
-            return (int)(r.pair_idx % (uint32_t)P);
-        }, order, start);
-        pool.run(P, [&](int part) {
-            std::unordered_map<uint32_t, int64_t> pending;      // pair -> read waiting for its mate
-            pending.reserve((start[(size_t)part + 1] - start[(size_t)part]) / 2 + 16);
-            for (size_t q = start[(size_t)part]; q < start[(size_t)part + 1]; q++) {
-                const size_t ri = order[q];
-                const Read &r = S.reads[ri];
-                auto it = pending.find(r.pair_idx);
-                if (it != pending.end() && S.reads[(size_t)it->second].ref_end <= r.pos) { pending.erase(it); it = pending.end(); }   // earlier read already left the buffer
-                if (it == pending.end()) pending.emplace(r.pair_idx, (int64_t)ri);
-                else {
-                    const size_t ai = (size_t)it->second;
-                    pending.erase(it);
-                    tweak_overlap(S, S.reads[ai], r);
-                }
+// What the drops mean for each read.  A read that some split dropped and another took keeps its place in the stream; its CIGAR is
+// rewritten so that it covers no column of the splits that dropped it -- M/=/X there become I + N, D becomes N -- and everything
+// downstream (overlap resolution, expansion) sees a read that is absent exactly there.  Dropped everywhere: removed.
+static void max_depth_rewrite(const isx_bam &B, Batch &S, int64_t WL, DepthDrops &D)
+{
+    std::vector<std::pair<uint32_t, int32_t>> &drops = D.drops;
+    std::vector<uint32_t> extra;                            // rewritten CIGARs, appended to S.cigars below
+    const size_t old_n = S.cigars.size();
+    std::sort(drops.begin(), drops.end());
+    for (size_t d = 0, d1; d < drops.size(); d = d1) {
+        const uint32_t ri = drops[d].first;
+        for (d1 = d; d1 < drops.size() && drops[d1].first == ri;) d1++;
+        Read &r = S.reads[ri];
+        if (D.n_drop[ri] >= D.n_seen[ri]) { r.pair_idx = 0xFFFFFFFFu; r.flag |= FUNMAP; continue; }     // no iterator took it
+        const Splits sp(B.ref_len[(size_t)r.tid], WL);
+        auto is_dropped = [&](int64_t c) { for (size_t k = d; k < d1; k++) if (drops[k].second == (int32_t)c) return true; return false; };
+        const uint64_t new_off = (uint64_t)old_n + extra.size();
+        int64_t rp = r.pos;
+        for (uint32_t k = 0; k < r.n_cigar; k++) {
+            const uint32_t cg = S.cigars[r.cigar_off + (uint64_t)k];
+            const uint32_t op = cg & 15u;
+            int64_t n = (int64_t)(cg >> 4);
+            if (!(OP_EATS[op] & EATS_R)) { extra.push_back(cg); continue; }          // consumes no reference: as it is
+            while (n > 0) {             // the operation cut at the split bounds it crosses
+                const int64_t c = rp >= 0 && rp < sp.sLen ? sp.of(rp) : -1;
+                const int64_t run = c < 0 ? n : std::min<int64_t>(n, sp.end(c) - rp + 1);
+                if (c >= 0 && is_dropped(c)) {
+                    if (OP_EATS[op] == EATS_BOTH) extra.push_back((uint32_t)(run << 4) | CI);
+                    extra.push_back((uint32_t)(run << 4) | CN);
+                } else extra.push_back((uint32_t)(run << 4) | op);
+                rp += run; n -= run;
             }
-        });
+        }
+        r.cigar_off = new_off;
+        r.n_cigar = (uint32_t)((uint64_t)old_n + extra.size() - new_off);
     }
-    stage("overlap resolution");
+    if (!extra.empty()) {
+        RawBuf<uint32_t> nb;
+        nb.resize(old_n + extra.size());
+        memcpy(nb.p, S.cigars.p, old_n * sizeof(uint32_t));
+        memcpy(nb.p + old_n, extra.data(), extra.size() * sizeof(uint32_t));
+        std::swap(nb.p, S.cigars.p);
+        std::swap(nb.n, S.cigars.n);
+    }
+}
 
-    // ---- which reads are piled up, dense pair ids in order of first appearance, and where every read's observations
-    //      start in the stream (count per read + prefix sums, all on the threads) ----
-    par_assign(pool, Q->emit, n_reads, (uint8_t)0);
-    std::vector<uint64_t> slot0(n_ref_all, 0);              // the batch's pair entries, reference after reference
+// false: the batch has too few reads for any column to be that deep (nothing was looked at)
+static bool apply_max_depth(BatchPlan &A)
+{
+    if (A.Q.S.reads.size() <= (size_t)MAX_DEPTH) return false;
+    if (const int64_t L = max_depth_screen(A)) {
+        const int64_t WL = window_length_of(*A.p);
+        DepthDrops D;
+        max_depth_replay(A.B, A.Q.S, L, WL, D);
+        max_depth_rewrite(A.B, A.Q.S, WL, D);
+    }
+    return true;
+}
+
+// ---- overlap_push in file order (htslib-1.9 rule |isize| < 2*l_qseq), partitioned by pair: a pair's two reads
+//      only ever touch each other's qualities ----
+static int resolve_overlaps(BatchPlan &A)
+{
+    Batch &S = A.Q.S;
+    const size_t n_reads = S.reads.size();
+    // candidates only (both mates mapped, proper pair, |isize| < 2 * l_qseq), bucketed by pair so that a task touches its
+    // own reads and not every read of the batch
+    const int P = Slices(A.pool, n_reads, 16384).nt;
+    std::vector<uint32_t> order;
+    std::vector<size_t> start;
+    if (n_reads >= 0xFFFFFFFFull) { isx_set_error("isx_bam_expand_refs: more than 2^32 reads in one batch"); return ISX_ERR_ARG; }
+    bucket_indices(A.pool, n_reads, P, [&](size_t ri) -> int {
+        const Read &r = S.reads[ri];
+        if (r.pair_idx == 0xFFFFFFFFu || (r.flag & FMUNMAP) || !(r.flag & FPROPER)) return -1;
+        if (std::abs((int64_t)r.isize) >= 2 * (int64_t)r.l_seq) return -1;
+        return (int)(r.pair_idx % (uint32_t)P);
+    }, order, start);
+    A.pool.run(P, [&](int part) {
+        std::unordered_map<uint32_t, int64_t> pending;      // pair -> read waiting for its mate
+        pending.reserve((start[(size_t)part + 1] - start[(size_t)part]) / 2 + 16);
+        for (size_t q = start[(size_t)part]; q < start[(size_t)part + 1]; q++) {
+            const size_t ri = order[q];
+            const Read &r = S.reads[ri];
+            auto it = pending.find(r.pair_idx);
+            if (it != pending.end() && S.reads[(size_t)it->second].ref_end <= r.pos) { pending.erase(it); it = pending.end(); }   // earlier read already left the buffer
+            if (it == pending.end()) pending.emplace(r.pair_idx, (int64_t)ri);
+            else {
+                const size_t ai = (size_t)it->second;
+                pending.erase(it);
+                tweak_overlap(S, S.reads[ai], r);
+            }
+        }
+    });
+    return ISX_OK;
+}
+
+// "is this read's pair in R2M" as ONE BIT per pair entry: the reads come in position order, their pair entries in hash order --
+// a look-up into the 72-byte entries is a DRAM miss per read (6 M reads: 20-40 ms of the hand-over), the bit plane stays in the L2
+// (only the words between the first and the last pair entry of the batch's references are made: a reference's entries are contiguous).
+// mm profiling on: Q.pair_mm, the pairs' levels as a 1-byte table, in the same sweep.
+static void mark_passing_pairs(BatchPlan &A, uvec<uint64_t> &pass_bits)
+{
+    isx_bam &B = A.B;
+    const size_t n_pair_all = B.pairs.size();
+    pass_bits.resize((n_pair_all + 63) / 64);
+    size_t p_lo = n_pair_all, p_hi = 0;
+    for (int32_t i = 0; i < A.n_refs; i++) { p_lo = std::min<size_t>(p_lo, (size_t)B.ref_pair0[(size_t)A.refs[i]]); p_hi = std::max<size_t>(p_hi, (size_t)B.ref_pair0[(size_t)A.refs[i] + 1]); }
+    const size_t w_lo = p_lo >> 6, n_words = p_hi > p_lo ? ((p_hi + 63) >> 6) - w_lo : 0;
+    const Slices sl(A.pool, n_words, 4096);
+    const bool want_mm = !A.p->skip_mm;
+    if (want_mm) { A.Q.pair_mm_lo = w_lo * 64; A.Q.pair_mm.resize(n_words * 64 + 64); }
+    uint8_t *pmm = want_mm ? A.Q.pair_mm.data() : nullptr;
+    A.pool.run(sl.nt, [&](int t) {
+        for (size_t wd = w_lo + sl.lo(t); wd < w_lo + sl.lo(t + 1); wd++) {
+            uint64_t m = 0;
+            const size_t i0 = wd * 64, i1 = std::min(n_pair_all, i0 + 64);
+            for (size_t i = i0; i < i1; i++) {
+                m |= (uint64_t)(B.pairs[i].pass && B.pairs[i].reads != 0) << (i - i0);
+                if (pmm) pmm[i - w_lo * 64] = (uint8_t)std::min<int32_t>(255, std::max<int32_t>(0, B.level_of(B.pairs[i].mm)));
+            }
+            pass_bits[wd] = m;
+        }
+    });
+}
+
+// ---- which reads are piled up, dense pair ids in order of first appearance, and where every read's observations (out_at) or
+//      segments (seg_at, seg_gpos) start in the stream: count per read + prefix sums, all on the threads ----
+static int number_pairs_and_count(BatchPlan &A, const uvec<uint64_t> &pass_bits)
+{
+    isx_bam &B = A.B;
+    isxenc::HostPool &pool = A.pool;
+    BamBatch *q = &A.Q;
+    const Batch &S = q->S;
+    const size_t n_reads = S.reads.size();
+    const bool as_segments = A.as_segments;
+    par_assign(pool, q->emit, n_reads, (uint8_t)0);
+    std::vector<uint64_t> slot0(B.ref_name.size(), 0);      // the batch's pair entries, reference after reference
     uint64_t n_slots = 0;
-    for (int32_t i = 0; i < n_refs; i++) { slot0[(size_t)refs[i]] = n_slots; n_slots += B.ref_pair0[(size_t)refs[i] + 1] - B.ref_pair0[(size_t)refs[i]]; }
+    for (int32_t i = 0; i < A.n_refs; i++) { slot0[(size_t)A.refs[i]] = n_slots; n_slots += B.ref_pair0[(size_t)A.refs[i] + 1] - B.ref_pair0[(size_t)A.refs[i]]; }
     // dense id of a pair = rank of its first piled-up read: per pair the smallest read index (atomic min, threads over
     // the reads), a prefix count of those first reads, then every read looks its pair's id up
     uvec<uint32_t> first, dense;
     par_assign(pool, first, (size_t)n_slots, 0xFFFFFFFFu);
     par_assign(pool, dense, (size_t)n_slots, 0xFFFFFFFFu);
-    par_assign(pool, Q->pid, n_reads, 0u);
-    const int n_tasks = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n_reads / 2048 + 1));
-    auto lo_of = [&](int t) { return n_reads * (size_t)t / (size_t)n_tasks; };
+    par_assign(pool, q->pid, n_reads, 0u);
+    const Slices sl(pool, n_reads, 2048);
+    const int n_tasks = sl.nt;
     auto slot_of = [&](const Read &r) -> size_t { return (size_t)(slot0[(size_t)r.tid] + (r.pair_idx - B.ref_pair0[(size_t)r.tid])); };
-    BamBatch *q = Q.get();
-    // "is this read's pair in R2M" as ONE BIT per pair entry: the reads come in position order, their pair entries in hash order --
-    // a look-up into the 72-byte entries is a DRAM miss per read (6 M reads: 20-40 ms of the hand-over), the bit plane stays in the L2
-    // (only the words between the first and the last pair entry of the batch's references are made: a reference's entries are contiguous)
-    const size_t n_pair_all = B.pairs.size();
-    uvec<uint64_t> pass_bits((n_pair_all + 63) / 64);
-    {
-        size_t p_lo = n_pair_all, p_hi = 0;
-        for (int32_t i = 0; i < n_refs; i++) { p_lo = std::min<size_t>(p_lo, (size_t)B.ref_pair0[(size_t)refs[i]]); p_hi = std::max<size_t>(p_hi, (size_t)B.ref_pair0[(size_t)refs[i] + 1]); }
-        const size_t w_lo = p_lo >> 6, n_words = p_hi > p_lo ? ((p_hi + 63) >> 6) - w_lo : 0;
-        const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.size() * 4, n_words / 4096 + 1));
-        const bool want_mm = !p->skip_mm;
-        if (want_mm) { Q->pair_mm_lo = w_lo * 64; Q->pair_mm.resize(n_words * 64 + 64); }
-        uint8_t *pmm = want_mm ? Q->pair_mm.data() : nullptr;
-        pool.run(nt, [&](int t) {
-            for (size_t wd = w_lo + n_words * (size_t)t / (size_t)nt; wd < w_lo + n_words * (size_t)(t + 1) / (size_t)nt; wd++) {
-                uint64_t m = 0;
-                const size_t i0 = wd * 64, i1 = std::min(n_pair_all, i0 + 64);
-                for (size_t i = i0; i < i1; i++) {
-                    m |= (uint64_t)(B.pairs[i].pass && B.pairs[i].reads != 0) << (i - i0);
-                    if (pmm) pmm[i - w_lo * 64] = (uint8_t)std::min<int32_t>(255, std::max<int32_t>(0, B.level_of(B.pairs[i].mm)));
-                }
-                pass_bits[wd] = m;
-            }
-        });
-    }
     pool.run(n_tasks, [&](int t) {
-        for (size_t ri = lo_of(t); ri < lo_of(t + 1); ri++) {
+        for (size_t ri = sl.lo(t); ri < sl.lo(t + 1); ri++) {
             const Read &r = S.reads[ri];
             // R2M membership is by NAME on this scaffold (get_base_counts_mm looks up query_name)
             if (r.pair_idx == 0xFFFFFFFFu) continue;
@@ -2714,13 +2822,13 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
     });
     std::vector<uint32_t> firsts((size_t)n_tasks + 1, 0);
     std::vector<uint64_t> outs((size_t)n_tasks + 1, 0), segs_of((size_t)n_tasks + 1, 0), cols_of((size_t)n_tasks + 1, 0);
-    par_assign(pool, Q->out_at, n_reads + 1, (uint64_t)0);
+    par_assign(pool, q->out_at, n_reads + 1, (uint64_t)0);
     uvec<uint32_t> seg_cnt;                         // segments of every read
-    if (as_segments) { Q->seg_at.resize(n_reads + 1); par_assign(pool, seg_cnt, n_reads, 0u); }      // (seg_at: every entry is written below)
+    if (as_segments) { q->seg_at.resize(n_reads + 1); par_assign(pool, seg_cnt, n_reads, 0u); }      // (seg_at: every entry is written below)
     pool.run(n_tasks, [&](int t) {
         uint32_t nf = 0;
         uint64_t no = 0, ns = 0, nc = 0;
-        for (size_t ri = lo_of(t); ri < lo_of(t + 1); ri++) {
+        for (size_t ri = sl.lo(t); ri < sl.lo(t + 1); ri++) {
             if (!q->emit[ri]) continue;
             nf += first[slot_of(S.reads[ri])] == (uint32_t)ri;
             if (as_segments) {                      // segments come from the CIGAR alone: no per-base pass
@@ -2736,12 +2844,12 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
         }
         firsts[(size_t)t + 1] = nf; outs[(size_t)t + 1] = no; segs_of[(size_t)t + 1] = ns; cols_of[(size_t)t + 1] = nc;
     });
-    for (int t = 0; t < n_tasks; t++) { segs_of[(size_t)t + 1] += segs_of[(size_t)t]; Q->n_seg_bases += (int64_t)cols_of[(size_t)t + 1]; }
+    for (int t = 0; t < n_tasks; t++) { segs_of[(size_t)t + 1] += segs_of[(size_t)t]; q->n_seg_bases += (int64_t)cols_of[(size_t)t + 1]; }
     if (as_segments) {
-        Q->seg_gpos.resize((size_t)segs_of[(size_t)n_tasks]);
+        q->seg_gpos.resize((size_t)segs_of[(size_t)n_tasks]);
         pool.run(n_tasks, [&](int t) {
             uint64_t at = segs_of[(size_t)t];
-            for (size_t ri = lo_of(t); ri < lo_of(t + 1); ri++) {
+            for (size_t ri = sl.lo(t); ri < sl.lo(t + 1); ri++) {
                 q->seg_at[ri] = at;
                 if (seg_cnt[ri]) q->for_segments(ri, [&](int64_t g, int64_t, int64_t) { q->seg_gpos[(size_t)at++] = (uint32_t)g; });
             }
@@ -2749,45 +2857,76 @@ int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs
         q->seg_at[n_reads] = segs_of[(size_t)n_tasks];
     }
     for (int t = 0; t < n_tasks; t++) { firsts[(size_t)t + 1] += firsts[(size_t)t]; outs[(size_t)t + 1] += outs[(size_t)t]; }
-    Q->next_pair = firsts[(size_t)n_tasks];
+    q->next_pair = firsts[(size_t)n_tasks];
     const bool keep_names = !B.seg_names.empty();           // (isx_bam_drop_names not called: somebody wants the names of the pair ids)
-    bam->last_dense_pair.assign(keep_names ? (size_t)Q->next_pair : 0, 0u);
-    uint32_t *dpair = bam->last_dense_pair.data();
+    B.last_dense_pair.assign(keep_names ? (size_t)q->next_pair : 0, 0u);
+    uint32_t *dpair = B.last_dense_pair.data();
     pool.run(n_tasks, [&](int t) {
         uint32_t nf = firsts[(size_t)t];
         uint64_t at = outs[(size_t)t];
-        for (size_t ri = lo_of(t); ri < lo_of(t + 1); ri++) {
+        for (size_t ri = sl.lo(t); ri < sl.lo(t + 1); ri++) {
             if (q->emit[ri]) {
-                const size_t sl = slot_of(S.reads[ri]);
-                if (first[sl] == (uint32_t)ri) { if (keep_names) dpair[nf] = S.reads[ri].pair_idx; dense[sl] = nf++; }
+                const size_t s = slot_of(S.reads[ri]);
+                if (first[s] == (uint32_t)ri) { if (keep_names) dpair[nf] = S.reads[ri].pair_idx; dense[s] = nf++; }
             }
             at += q->out_at[ri + 1];
             q->out_at[ri + 1] = at;
         }
     });
     pool.run(n_tasks, [&](int t) {
-        for (size_t ri = lo_of(t); ri < lo_of(t + 1); ri++)
+        for (size_t ri = sl.lo(t); ri < sl.lo(t + 1); ri++)
             if (q->emit[ri]) q->pid[ri] = dense[slot_of(S.reads[ri])];
     });
-    if (Q->out_at.back() >= 0xFFFFFFFFull) { isx_set_error("isx_bam_expand_refs: more than 2^32 observations in one batch (expand fewer references at a time)"); return ISX_ERR_ARG; }
-    stage("count");
+    if (q->out_at.back() >= 0xFFFFFFFFull) { isx_set_error("isx_bam_expand_refs: more than 2^32 observations in one batch (expand fewer references at a time)"); return ISX_ERR_ARG; }
+    return ISX_OK;
+}
 
-    // ---- iterate_splits (fasta.py:56-73) on the batch's flat space ----
-    const int64_t W = p->window_length > 0 ? p->window_length : 10000;
-    for (int32_t i = 0; i < n_refs; i++) {
-        const size_t t = (size_t)refs[i];
-        const int64_t sLen = B.ref_len[t];
-        if (sLen <= 0) continue;
-        const int64_t n_chunks = sLen / W + 1;
-        const int64_t chunk = (int64_t)((double)sLen / (double)n_chunks);
-        int64_t start = 0;
-        for (int64_t c = 0; c < n_chunks; c++) {
-            Q->split_bounds.push_back(boff[t] + start);
-            Q->split_ref.push_back((int32_t)t);
-            if (c + 1 < n_chunks) start += chunk;
+// ---- iterate_splits (fasta.py:56-73) on the batch's flat space ----
+static void lay_out_splits(BatchPlan &A)
+{
+    const int64_t W = window_length_of(*A.p);
+    for (int32_t i = 0; i < A.n_refs; i++) {
+        const size_t t = (size_t)A.refs[i];
+        if (A.B.ref_len[t] <= 0) continue;
+        const Splits sp(A.B.ref_len[t], W);
+        for (int64_t c = 0; c < sp.n; c++) {
+            A.Q.split_bounds.push_back(A.Q.boff[t] + sp.start(c));
+            A.Q.split_ref.push_back((int32_t)t);
         }
     }
-    Q->split_bounds.push_back(n_pos);
+    A.Q.split_bounds.push_back(A.Q.n_pos);
+}
+
+int bam_batch_prepare(isx_bam *bam, const isx_bam_params *p, const int32_t *refs, int32_t n_refs, BamBatch **out, int64_t reg_lo, int64_t reg_hi,
+                      bool as_segments)
+{
+    *out = nullptr;
+    isx_bam &B = *bam;
+    if (!B.scanned || !B.filtered) { isx_set_error("isx_bam_expand_refs: scan and filter first"); return ISX_ERR_STATE; }
+    const bool timing = getenv("ISX_BAM_TIMING") != nullptr;       // tuning aid: stage times on stderr (no effect on results)
+    auto t_last = std::chrono::steady_clock::now();
+    auto stage = [&](const char *what) {
+        if (!timing) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[isx_bam_expand_refs] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    };
+    std::unique_ptr<BamBatch> Q(new BamBatch());
+    Q->B = bam; Q->prm = *p;
+    Q->minq = (uint8_t)std::min(255, std::max(0, p->min_base_quality));
+    BatchPlan A{B, *Q, pool_of(B), p, refs, n_refs, reg_hi >= 0, as_segments, {}};
+    int rc;
+    if ((rc = plan_batch(A, reg_lo, reg_hi)) != ISX_OK) return rc;
+    if ((rc = load_reads(A)) != ISX_OK) return rc;
+    stage("load reads");
+    if (apply_max_depth(A)) stage("max_depth");
+    if ((rc = resolve_overlaps(A)) != ISX_OK) return rc;
+    stage("overlap resolution");
+    uvec<uint64_t> pass_bits;
+    mark_passing_pairs(A, pass_bits);
+    if ((rc = number_pairs_and_count(A, pass_bits)) != ISX_OK) return rc;
+    stage("count");
+    lay_out_splits(A);
     {
         std::lock_guard<std::mutex> lk(bam->retire_mu);
         bam->batches_out++;

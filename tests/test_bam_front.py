@@ -657,3 +657,123 @@ def test_max_depth_is_replayed_per_split(tmp_path):
     assert (want == got).all()
     # a read pair's observations: the same multiset of per-pair counts
     assert sorted(np.bincount(pr).tolist()) == sorted(np.bincount(pair_id).tolist())
+
+
+SEAM_REFS = [("sA", 3000), ("sB", 40000)]
+SEAM_KW = dict(min_read_ani=0.5, max_insert_relative=1e9)
+SEAM_W = 1000
+
+
+def seam_reads():
+    """Reads for the seams of the aligned-run walk: M runs of 149, 150, 151, 300 and 301 columns (the cut every ISX_SEG_BASES = 150
+    columns falls before the run's last column, on it, and 1, 150 and 151 columns past it), CIGARs that mix = X I D N S H P, a pair
+    that overhangs the end of sA, and a pair at a known place on sB for the region cuts."""
+    rng = np.random.Generator(np.random.PCG64(77))
+    templates = [
+        [("M", 149)], [("M", 150)], [("M", 151)], [("M", 300)], [("M", 301)],
+        [("H", 3), ("S", 4), ("=", 40), ("I", 3), ("X", 20), ("D", 2), ("M", 149), ("N", 10), ("P", 1), ("M", 151), ("S", 6), ("H", 2)],
+        [("S", 7), ("M", 100), ("P", 2), ("I", 1), ("D", 5), ("=", 300), ("N", 3), ("X", 151)],
+    ]
+    reads = []
+
+    def pair(name, tid, s1, s2, c1, c2):
+        ends = []
+        for mate, (s, ops) in enumerate(((s1, c1), (s2, c2))):
+            qlen = sum(n for op, n in ops if op in "MIS=X")
+            seq = "".join(rng.choice(list("ACGTN"), qlen, p=[.245, .245, .245, .245, .02]))
+            qual = rng.choice([2, 29, 30, 37, 40], qlen, p=[.05, .1, .15, .4, .3])
+            ends.append(s + sum(n for op, n in ops if op in "MDN=X"))
+            reads.append(dict(tid=tid, pos=s, mapq=40, flag=0x1 | 0x2 | (0x40 if mate == 0 else 0x80), name=name, cigar=ops, seq=seq,
+                              qual=qual, nm=int(rng.integers(0, 4)), isize=0))
+        reads[-2]["isize"] = max(ends) - s1
+        reads[-1]["isize"] = -(max(ends) - s1)
+
+    for p in range(1000):
+        tid = int(rng.integers(0, 2))
+        s1 = int(rng.integers(0, SEAM_REFS[tid][1] - 900))
+        pair("p%d" % p, tid, s1, s1 + int(rng.integers(0, 250)), templates[p % 7], templates[int(rng.integers(0, 7))])
+    pair("overhang", 0, 2900, 2950, [("M", 300)], [("S", 2), ("M", 301)])        # both run past sA's last column
+    pair("cut", 1, 10000, 10050, [("M", 301)], [("M", 300)])
+    reads.sort(key=lambda r: (r["tid"], r["pos"]))
+    return reads
+
+
+def planes_to_obs(planes, segs):
+    """[n, 8] uint64 bit planes (mm profiling on) -> (gpos, base) like util.segs_to_obs: the observed columns carry their 2-bit code, a
+    column that is not observed but holds code 1 is a non-ACGT base that passed the quality filter (base 4)"""
+    j = np.arange(150)
+    code = (planes[:, j // 32] >> (2 * (j % 32)).astype(np.uint64)) & np.uint64(3)
+    skip = ((planes[:, 5 + j // 64] >> (j % 64).astype(np.uint64)) & np.uint64(1)).astype(bool)
+    live = j[None, :] < segs.len[:, None]
+    si, off = np.nonzero(live & (~skip | (code == 1)))
+    return segs.gpos[si].astype(np.int64) + off, np.where(skip[si, off], 4, code[si, off]).astype(np.uint8)
+
+
+@pytest.fixture(scope="module")
+def seam_case(tmp_path_factory):
+    """the BAM of seam_reads() and the oracle's stream for it, computed once"""
+    from oracle import bam_py
+    from tests import bamwriter
+    path = str(tmp_path_factory.mktemp("seams") / "seams.bam")
+    bamwriter.write_bam(path, SEAM_REFS, seam_reads())
+    _, rr = bam_py.read_bam(path)
+    r2m, _ = bam_py.filter_pairs({r[0]: bam_py.get_paired_reads(rr, t) for t, r in enumerate(SEAM_REFS)}, **SEAM_KW)
+    P, B, M, R, bounds, sref = [], [], [], [], [], []
+    off = nid = 0
+    for t, (name, ln) in enumerate(SEAM_REFS):
+        bam_py.resolve_overlaps(rr, t)
+        pos, base, mm, pr, n2i = bam_py.expand_observations(rr, t, r2m[name], ref_len=ln)
+        P.append(pos + off); B.append(base); M.append(mm); R.append(pr + nid)
+        bounds += [off + s for s, _ in bam_py.iterate_splits(ln, SEAM_W)]
+        sref += [t] * len(bam_py.iterate_splits(ln, SEAM_W))
+        off += ln
+        nid += len(n2i)
+    want = dict(gpos=np.concatenate(P), base=np.concatenate(B), mm=np.concatenate(M), pair=np.concatenate(R),
+                bounds=bounds + [off], sref=sref)
+    return path, want
+
+
+@pytest.mark.parametrize("threads", [1, 3])
+def test_cigar_walk_seams_against_the_oracle(seam_case, threads):
+    """The three consumers of the aligned-run walk (observation count, observation walk, read segments) and the range walks of the
+    three emitters, on reads built for their seams, against oracle/bam_py.py.  More than 65 536 observations and more than 4096
+    segments: the pieces expand and segment_refs hand to the threads begin inside reads (the emitters' skip > 0 branches).
+    Already covered elsewhere, with 60-column reads only: mixed = X I D N S H operations and overhanging reads
+    (test_random_messy_bam_cpp_equals_oracle_python, test_messy_bam_segments_equal_observations), region cuts of short runs
+    (test_expand_region_equals_the_cut_of_the_whole_reference); new here: runs that reach the 150-column cut, the P operation, a
+    region that cuts one run at both ends, and pieces that start inside a multi-segment read."""
+    path, want = seam_case
+    bam = engine.BamFile(path, threads=threads)
+    obs, pair, bounds, sref = bam.expand(window_length=SEAM_W, **SEAM_KW)
+    assert len(obs) == len(want["gpos"]) > 65536
+    assert (obs["gpos"] == want["gpos"]).all() and (obs["base"] == want["base"]).all() and (obs["mm"] == want["mm"]).all()
+    assert (pair == want["pair"]).all()
+    assert list(bounds) == want["bounds"] and list(sref) == want["sref"]
+    # the same batch as read segments and as bit planes
+    segs, b2, s2 = bam.segment_refs([0, 1], window_length=SEAM_W, **SEAM_KW)
+    planes = bam.read_planes()
+    assert segs.n_seg > 4096 and segs.len.max() == 150 and list(b2) == want["bounds"] and list(s2) == want["sref"]
+    g, b, m, p = util.segs_to_obs(segs)
+    assert len(g) == len(obs)
+    assert (g == obs["gpos"]).all() and (b == obs["base"]).all() and (m == obs["mm"]).all() and (p == pair).all()
+    pg, pb = planes_to_obs(planes, segs)
+    assert len(pg) == len(obs) and (pg == obs["gpos"]).all() and (pb == obs["base"]).all()
+    # a read's runs are cut every 150 columns and nowhere else: 301 columns are 150 + 150 + 1
+    at = int(np.nonzero(segs.gpos == 3000 + 10000)[0][0])
+    assert segs.len[at:at + 3].tolist() == [150, 150, 1]
+    # regions: the pair "cut" (301M at 10000, 300M at 10050) cut at both ends inside a run, on and around the 150-column cut;
+    # the overhanging pair of sA through a window that reaches past the scaffold's end
+    for ref, off, windows in ((1, 3000, ((10100, 10180), (10149, 10151), (10150, 10301), (10299, 10400), (0, 40000))),
+                              (0, 0, ((2899, 2901), (2990, 5000)))):
+        o, pr_all, _, _ = bam.expand_refs([ref], **SEAM_KW)
+        whole = want["gpos"][(want["gpos"] >= off) & (want["gpos"] < off + SEAM_REFS[ref][1])] - off
+        assert (o["gpos"] == whole).all()
+        for lo, hi in windows:
+            ro, rp, _, _ = bam.expand_region(ref, lo, hi, **SEAM_KW)
+            k = (o["gpos"] >= lo) & (o["gpos"] < hi)
+            assert len(ro) == k.sum() > 0 and (ro == o[k]).all(), (ref, lo, hi)
+            # pair ids are dense per expansion (a fetched read without a column in the window takes one too): same partition
+            _, fa, a = np.unique(rp, return_index=True, return_inverse=True)
+            _, fc, c = np.unique(pr_all[k], return_index=True, return_inverse=True)
+            assert (fa[a] == fc[c]).all(), (ref, lo, hi)
+    bam.close()

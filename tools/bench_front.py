@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the host BAM front end (isx_bam_open / isx_bam_expand): synthetic 2x150 bp pairs,
 written with a vectorised BAM writer; then the read filter (isx_bam_filter) and the read report after it
-(isx_bam_read_report), five handles each.  usage: python tools/bench_front.py [n_pairs] [genome_len] [n_refs]"""
+(isx_bam_read_report) and pass 2 alone as observations (isx_bam_expand_refs) and as read segments + bit planes
+(isx_bam_segment_refs), five handles each.  usage: python tools/bench_front.py [n_pairs] [genome_len] [n_refs] [threads]"""
 import os, struct, sys, time, zlib
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -76,9 +77,11 @@ if __name__ == "__main__":
         gbp = n_pairs * 300 / 1e9
         print("open %.3f s  expand %.3f s  -> %.3f Gbp/s  (%d obs, %.1f M reads/s)" %
               (t1 - t0, t2 - t1, gbp / (t2 - t0), n_obs, 2 * n_pairs / (t2 - t0) / 1e6), flush=True)
-    # the read filter and the read report that follows it (both host only), each on a fresh handle
+    # the read filter and the read report that follows it (both host only), then pass 2 on its own in both forms -- observations
+    # (expand_refs) and read segments with their bit planes (segment_refs) -- each on a fresh handle
+    threads = int(sys.argv[4]) if len(sys.argv) > 4 else 0
     for rep in range(5):
-        bf = engine.BamFile(path)
+        bf = engine.BamFile(path, threads=threads)
         t0 = time.perf_counter()
         bf.scan()
         t1 = time.perf_counter()
@@ -89,5 +92,13 @@ if __name__ == "__main__":
             rows = bf.read_report()
             t3 = time.perf_counter()
             line += "  read_report_ms %.2f  (%d entries went through the pairing filter)" % (1e3 * (t3 - t2), int(rows["pass_pairing_filter"].sum()))
+        refs = np.arange(len(bf.refs()), dtype=np.int32)
+        t4 = time.perf_counter()
+        obs, pair, _, _ = bf.expand_refs(refs, copy=False)
+        t5 = time.perf_counter()
+        del obs, pair
+        segs, _, _ = bf.segment_refs(refs)
+        t6 = time.perf_counter()
+        line += "  expand_refs_ms %.1f  segment_refs_ms %.1f  (%d segments)" % (1e3 * (t5 - t4), 1e3 * (t6 - t5), segs.n_seg)
         bf.close()
         print(line, flush=True)
