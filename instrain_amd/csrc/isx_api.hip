@@ -1356,20 +1356,21 @@ int launch_pass(isx_batch *b)
     a.counts = b->d_counts; a.clon = b->d_clon; a.clon_r = b->d_clon_r;
     a.min_cov_r = b->prm.rarefied_coverage;
     a.cov16 = b->d_cov16; a.rare = b->d_rare; a.cap_rare = (uint32_t)std::min<size_t>(b->cap_rare, 0xFFFFFFFFu);
-    a.cov8 = b->sparse_out && b->cov8_out ? b->d_cov8 : nullptr;
+    PassForm &f = b->form;
+    a.cov8 = f.sparse_out && f.cov8_out ? b->d_cov8 : nullptr;
     a.sat = b->d_sat; a.cap_sat = (uint32_t)std::min<size_t>(b->cap_sat, 0xFFFFFFFFu); a.sat_thr = a.cov8 ? 255u : 65535u;
-    b->nib_pass = false;
-    if (b->sparse_out && b->nib_out && b->lean && b->drec && b->packed && b->M == 1 && b->d_cov_row_win && b->d_cov8 &&
+    f.nib_pass = false;
+    if (f.sparse_out && f.nib_out && b->lean && b->drec && b->packed && b->M == 1 && b->d_cov_row_win && b->d_cov8 &&
         (size_t)b->n_win <= b->cap_cov_row_win) {      // 4-bit plane + rows: the two coverage buffers change their roles
-        b->nib_pass = true;
+        f.nib_pass = true;
         a.cov4 = b->d_cov8; a.cov_rows = b->d_cov16; a.cov_row_win = b->d_cov_row_win;
         a.cap_cov_rows = (uint32_t)std::min<uint64_t>((uint64_t)(b->cap_pos ? b->cap_pos : b->n_pos), 0xFFFFFFFFu);
         a.cov8 = nullptr; a.cov16 = nullptr; a.sat_thr = 65535u;
     }
-    a.clon_list = b->sparse_out ? b->d_clon_list : nullptr; a.cap_clon = (uint32_t)std::min<size_t>(b->cap_clon, 0xFFFFFFFFu);
-    if (b->lean && b->sparse_out) {             // a lean slot writes only what travels home
-        if (!b->clon_dense) a.clon = nullptr;
-        if (!b->rare_dense && a.rare) a.clon_r = nullptr;
+    a.clon_list = f.sparse_out ? b->d_clon_list : nullptr; a.cap_clon = (uint32_t)std::min<size_t>(b->cap_clon, 0xFFFFFFFFu);
+    if (b->lean && f.sparse_out) {              // a lean slot writes only what travels home
+        if (!f.clon_dense) a.clon = nullptr;
+        if (!f.rare_dense && a.rare) a.clon_r = nullptr;
         if (a.cov8) a.cov16 = nullptr;
     }
 #ifdef ISX_TUNING
@@ -1381,9 +1382,9 @@ int launch_pass(isx_batch *b)
     a.ovf0 = (uint64_t)b->n_win * b->slab; a.win_nent = b->d_win_nent;
     if (b->lev_sparse) {                        // mm path of a pipe slot: the levels go home as mask + coverage bytes + lists (PileupArgs::lev_*)
         a.lev_mask = b->d_lev_mask; a.lev_cov = b->d_lev_cov; a.lev_win_off = b->d_lev_win_off;
-        a.lev_mask_bytes = b->lev_mask_bytes; a.lev_cov_bytes = b->lev_cov_bytes;
+        a.lev_mask_bytes = b->lev_mask_bytes; a.lev_cov_bytes = f.lev_cov_bytes;
         a.cap_lev = (uint32_t)std::min<size_t>(b->cap_lev, 0xFFFFFFFEu);
-        a.sat_thr = b->lev_cov_bytes == 1 ? 255u : 65535u;
+        a.sat_thr = f.lev_cov_bytes == 1 ? 255u : 65535u;
         a.clon_list = b->d_clon_list; a.cap_clon = (uint32_t)std::min<size_t>(b->cap_clon, 0xFFFFFFFFu);
         a.cov16 = nullptr; a.cov8 = nullptr; a.clon = nullptr; a.clon_r = nullptr;
     }

@@ -32,6 +32,19 @@ struct isx_ctx {
 // a queue for what is NOT a pass (copy-in, finishers' chains, copy-out): on the reserved CUs when the context keeps some (isx_api.hip)
 hipError_t isx_side_stream_create(isx_ctx *c, hipStream_t *s);
 
+// The form in which a pipe slot's pass writes the tables that travel home.  isx_pipe.hip owns it: form_for_depth picks it from the
+// batch's mean depth, form_revise changes it after a pass whose lists overflowed (the pass is then repeated), form_landed says what
+// the finisher brought home.  launch_pass turns it into kernel arguments and notes in nib_pass what it really did.
+struct PassForm {
+    bool sparse_out = false;            // dense path without a count table: write the clonality list (the values other than 1.0)
+    bool cov8_out = false;              // ... and coverage in one byte (+ the exact coverage of the positions at 255 or beyond in d_sat)
+    bool nib_out = false;               // lean slots: coverage as the 4-bit plane (in d_cov8) + 16-bit rows of the windows beyond 15 (in d_cov16)
+    bool nib_pass = false;              // the last pass really wrote that plane (nib_out asked for, and the kernel is the packed reference-delta one)
+    bool clon_dense = false;            // lean slots: write the dense clonality array too (the list did not fit, or did not pay)
+    bool rare_dense = true;             // write the dense clonTR array (false: a lean slot's shallow batch, the list alone)
+    int lev_cov_bytes = 1;              // level-sparse slots: bytes of a level's coverage (1 for a batch shallower than 64x, else 2)
+};
+
 struct isx_batch {
     isx_ctx *ctx = nullptr;
     isx_params prm{};
@@ -83,15 +96,12 @@ struct isx_batch {
     uint32_t n_clon = 0;
     int spin_us = 2000;                 // finish_pass: how long the finisher polls the epoch word before it falls back to a stream wait (a pipe
                                         // whose caller gave it few host threads -- a rank of a multi-GPU job on a shared CPU quota -- polls briefly)
-    bool nib_pass = false;              // the last pass really wrote the 4-bit plane (nib_out asked for, and the kernel is the packed reference-delta one)
-    bool nib_out = false;               // this pass: coverage as the 4-bit plane (in d_cov8) + 16-bit rows of the windows beyond 15 (in d_cov16): lean slots
-    uint32_t *d_cov_row_win = nullptr;  // ... and the window of every such row
+    PassForm form;                      // what the next pass is asked to write (a one-shot batch keeps the defaults)
+    uint32_t *d_cov_row_win = nullptr;  // the 4-bit plane's 16-bit rows (PassForm::nib_out): the window of every row
     size_t cap_cov_row_win = 0;
     uint32_t n_cov_rows = 0;
-    bool sparse_out = false, cov8_out = false;   // this pass: write the sparse clonality list / the 1-byte coverage
-    bool rare_dense = true;             // this pass writes the dense clonTR array (a lean slot's shallow batch: the list alone; finish_slot repeats the pass otherwise)
-    bool lean = false, clon_dense = false;       // lean slot (isx_pipe_params.lean_output): the dense clonality array / the 16-bit coverage
-                                                 // are written only when a batch needs them (clon_dense: its clonality list did not fit)
+    bool lean = false;                  // lean slot (isx_pipe_params.lean_output): the dense clonality / clonTR arrays and the 16-bit coverage
+                                        // are written only when a batch needs them
     // mm path, level-sparse hand-back (pipe slots with n_mm_bins <= 32 and no want_counts; PileupArgs::lev_*): per position the mask of its
     // levels, per present level its coverage in lev_cov_bytes (1 for a batch shallower than 64x, else 2), the window's first level index;
     // d_clon_list / d_rare / d_sat then hold (level index, value).  d_entries is a FLAT table indexed by level (handed to the consumers of
@@ -100,7 +110,7 @@ struct isx_batch {
     void *d_lev_mask = nullptr, *d_lev_cov = nullptr;
     uint32_t *d_lev_win_off = nullptr;
     size_t cap_lev = 0;
-    int lev_mask_bytes = 0, lev_cov_bytes = 1;
+    int lev_mask_bytes = 0;
     isx_entry *d_entries = nullptr;  // mm path: [n_win][slab] slabs, then cap_ovf overflow entries
     uint32_t *d_win_nent = nullptr;
     uint32_t *d_win_site_base = nullptr, *d_win_site_cnt = nullptr;    // k_pileup_mm with linkage: a window's range in the site table

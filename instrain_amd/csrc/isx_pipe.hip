@@ -63,10 +63,13 @@ void host_block_free(void *p, bool pinned)
 }
 
 static const bool pipe_timing = getenv("ISX_PIPE_TIMING") != nullptr;     // tuning aid (stderr only), set from outside the process: read once
-#define H2D(p, s) ((s).h2d ? (s).h2d : (p)->s_h2d)
-struct Slot {
-    isx_batch *b = nullptr;
-    hipStream_t h2d = nullptr;              // this slot's copy-in queue when the pipe has two (else the pipe's)
+constexpr int PIPE_FINISHERS_DEEP = 4;                 // finisher threads of a pipe of depth >= 4 (two below that; never more than slots)
+constexpr size_t LEV_KERNEL_MAX = (size_t)32 << 20;     // a level-sparse batch whose whole hand-back is at most this leaves by copy kernel
+
+// A slot has three parts, by who writes them.
+// The copy-in side.  Written by the thread that submits (the caller, or the stager) between slot_acquire and enqueue_pass, while the slot
+// is free; its sizes and layout by isx_pipe_create.  (isx_pipe_collect reads the events and statistics, pipe_fetch_entries borrows h_in.)
+struct SlotIn {
     uint8_t *h_in = nullptr, *d_in = nullptr;
     size_t in_bytes = 0;                    // of the device arena; the pinned one ends after the ring when the pipe stages through one
     size_t off_bounds = 0, off_win = 0, off_ref = 0, off_gbase = 0, off_ridx = 0, off_rec = 0;   // records last
@@ -78,48 +81,73 @@ struct Slot {
     size_t cap_runs = 0;
     hipEvent_t ev_ring[2] = {nullptr, nullptr};     // ring mode: the copy that last read each half
     bool ring_busy[2] = {false, false};
-    uint8_t *h_out = nullptr;
-    uint8_t *h_small = nullptr;             // always pinned: the first SNV rows and clonTR entries (o_snv, o_rare are offsets into it)
-    size_t small_bytes = 0;
-    bool out_pinned = true;                 // false: the dense arrays go to plain memory through the pipe's bounce buffers (see slot_batch_create)
-    size_t out_bytes = 0, o_counts = 0, o_clon = 0, o_clonr = 0, o_snv = 0, o_cov16 = 0, o_rare = 0;
-    bool rare_dense = false;                // the clonTR table of the last batch went back as the dense array
-    bool cov8 = false, clon_sparse = false; // how the last (shallow) batch's coverage / clonality went back
+    std::vector<uint32_t> cmin, cmax, dir_pmax, dir_smin;     // the encoder's chunk directory (dir_*: scratch of the window directory)
+    std::vector<uint8_t> cany;
+    std::vector<uint2> win;
+    hipEvent_t ev_h2d0 = nullptr, ev_h2d1 = nullptr;
+    hipEvent_t ev_h2da = nullptr, ev_h2db = nullptr;   // a copy-in in two parts (the reference leaves before the records exist): end of the first, start of the second
+    bool h2d_split = false;
+    bool ref_has_n = false;                 // the batch's reference holds positions that are not A/C/T/G: their bit plane travels too
+    float encode_ms = 0.f;
+    int encode_passes = 0;
+    int64_t h2d_bytes = 0;
+    uint16_t *d_gpos16 = nullptr;           // compact stream + linkage: positions alone for the allele pass
+};
+
+// What a finished batch's tables came home as (form_landed): the only record isx_pipe_collect reads to hand them out.  Not the PassForm
+// the pass was asked for: a list that overflowed its table, or does not pay, goes back as the array although the pass wrote both.
+struct LandedForm {
+    bool cov8 = false, clon_sparse = false; // a shallow batch's coverage in one byte / clonality as the sorted list
     bool cov4 = false;                      // ... coverage as the 4-bit plane + 16-bit rows (lean slots): rows at h_out + o_cov16 + cov_rows_off
     size_t cov_rows_off = 0;
     int cov_window = 0;
+    bool rare_dense = false;                // the clonTR table went back as the dense array
+    bool sat_complete = true;               // every saturated position's exact coverage is in sat_rows
+    int lev_cov_bytes = 1;                  // level-sparse slots: bytes of a level's coverage
+};
+
+// The result side.  Written by the finisher thread that took the slot's ticket, between state 1 and state 2 (the three events: by the
+// submitting thread in enqueue_pass, under launch_mu); its layout by isx_pipe_create.  isx_pipe_collect reads it in state 2.
+struct SlotOut {
+    uint8_t *h_out = nullptr;
+    uint8_t *h_small = nullptr;             // always pinned: the first SNV rows and clonTR entries (o_snv, o_rare are offsets into it)
+    size_t small_bytes = 0;
+    bool out_pinned = true;                 // false: the dense arrays go to plain memory through the pipe's bounce buffers (see slot_result_blocks)
+    size_t out_bytes = 0, o_counts = 0, o_clon = 0, o_clonr = 0, o_snv = 0, o_cov16 = 0, o_rare = 0;
+    // mm path, level-sparse hand-back (isx_batch::lev_sparse): offsets into h_out and the bytes of each region
+    size_t o_lmask = 0, o_lwin = 0, o_lcov = 0, o_lclon = 0, o_lrare = 0;
+    size_t lcov_room = 0, lclon_room = 0, lrare_room = 0;
+    LandedForm landed;
     std::vector<uint32_t> cov_row_win;
-    std::vector<isx_sat> sat_rows;          // exact coverage of its saturated positions
-    bool sat_complete = true;
+    std::vector<isx_sat> sat_rows;          // exact coverage of the batch's saturated positions
     void *sort_temp = nullptr;              // device scratch of the clonality list's sort
     size_t sort_temp_bytes = 0;
-    std::vector<float> clonr_big;           // that array when the pipe has no pinned room for it (no want_counts)
+    std::vector<float> clonr_big;           // the dense clonTR array when the pipe has no pinned room for it (no want_counts)
     std::vector<isx_rare> rare_big;         // more clonTR entries than the pinned block holds / the device list overflowed
-    std::vector<uint32_t> cmin, cmax, dir_pmax, dir_smin;     // (dir_*: scratch of the window directory)
-    std::vector<uint8_t> cany;
-    std::vector<uint2> win;
-    // mm path, level-sparse hand-back (isx_batch::lev_sparse): offsets into h_out and how much of each region the last batch used
-    size_t o_lmask = 0, o_lwin = 0, o_lcov = 0, o_lclon = 0, o_lrare = 0;
-    size_t lcov_room = 0, lclon_room = 0, lrare_room = 0;          // bytes
     std::vector<uint8_t> lcov_big;          // a batch whose coverage stream / lists outgrow the pinned rooms (a deep sample)
     std::vector<isx_rare> lclon_big, lrare_big;
     std::vector<isx_snv> snv_big;           // more SNV rows than the pinned block holds (rare)
-    std::vector<isx_ld> ld_rows;            // the batch's LD rows (linkage), fetched by the finisher
+    std::vector<isx_ld> ld_rows;            // the batch's LD rows (linkage)
     uint64_t rows_checksum = 0;             // over the SNV + LD rows' bytes (isx_pipe_result.rows_checksum)
-    hipEvent_t ev_h2d0 = nullptr, ev_h2d1 = nullptr, ev_pass = nullptr, ev_d2h0 = nullptr, ev_d2h1 = nullptr;
-    hipEvent_t ev_h2da = nullptr, ev_h2db = nullptr;   // a copy-in in two parts (the reference leaves before the records exist): end of the first, start of the second
-    bool h2d_split = false;
+    hipEvent_t ev_pass = nullptr, ev_d2h0 = nullptr, ev_d2h1 = nullptr;
+    float finish_wait_ms = 0.f;
+    int64_t d2h_bytes = 0;
+};
+
+// The ticket and its state.  Every field is read and written under isx_pipe::mu only.
+struct SlotTicket {
     int64_t ticket = -1;
-    BamBatch *dead_batch = nullptr;         // isx_pipe_submit_bam: the front end's batch, freed by the finisher after the slot's work
-    bool ref_has_n = false;                 // the batch's reference holds positions that are not A/C/T/G: their bit plane travels too
     int state = 0;                          // 0 free, 1 submitted, 2 finished (tables on the host, linkage done)
     int rc = 0;                             // of the finishing step
     std::string err;
-    float finish_wait_ms = 0.f;
-    float encode_ms = 0.f;
-    int encode_passes = 0;
-    int64_t h2d_bytes = 0, d2h_bytes = 0;
-    uint16_t *d_gpos16 = nullptr;           // compact stream + linkage: positions alone for the allele pass
+    BamBatch *dead_batch = nullptr;         // isx_pipe_submit_bam: the front end's batch, freed by the finisher after the slot's work
+};
+
+struct Slot {
+    isx_batch *b = nullptr;                 // the device tables: made by isx_pipe_create; whoever holds the slot (submit, then its finisher) drives it
+    SlotIn in;
+    SlotOut res;
+    SlotTicket tk;
 };
 
 // order-sensitive 64-bit checksum of a table's bytes (four multiply-add lanes over its 64-bit words: ~20 GB/s on one core)
@@ -237,7 +265,6 @@ struct isx_pipe {
     std::unique_ptr<isxenc::HostPool> pool;
     std::vector<Slot> slots;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    hipStream_t s_h2d2 = nullptr;           // ISX_PIPE_H2D_STREAMS=2: the odd slots' copy-in queue (a second copy engine)
     hipStream_t s_fin = nullptr;            // the finishers' own queues: what they fetch must not wait behind the copy-outs of later batches
     hipStream_t s_fin2 = nullptr;           // (one per finisher thread: a sync of one must not wait for the other's 30 MB table)
     int64_t next_ticket = 0;
@@ -337,7 +364,6 @@ static void pipe_free(isx_pipe *p)
     }
     (void)hipSetDevice(p->ctx->device);
     if (p->s_h2d) (void)isx_wait_stream(p->s_h2d);
-    if (p->s_h2d2) (void)isx_wait_stream(p->s_h2d2);
     if (p->s_d2h) (void)isx_wait_stream(p->s_d2h);
     if (p->s_fin) (void)isx_wait_stream(p->s_fin);
     if (p->s_fin2) (void)isx_wait_stream(p->s_fin2);
@@ -357,18 +383,18 @@ static void pipe_free(isx_pipe *p)
             isx_batch_destroy(b);
         }
         t_batch += now_ms() - t_x; t_x = now_ms();
-        if (s.sort_temp) isx_dev_free(s.sort_temp);
-        if (s.d_gpos16) isx_dev_free(s.d_gpos16);
-        if (s.d_in) isx_dev_free(s.d_in);
-        if (s.d_runs) isx_dev_free(s.d_runs);
+        if (s.res.sort_temp) isx_dev_free(s.res.sort_temp);
+        if (s.in.d_gpos16) isx_dev_free(s.in.d_gpos16);
+        if (s.in.d_in) isx_dev_free(s.in.d_in);
+        if (s.in.d_runs) isx_dev_free(s.in.d_runs);
         t_dev += now_ms() - t_x; t_x = now_ms();
-        if (s.h_in) isx_pin_free(s.h_in);
-        host_block_free(s.h_runs, s.runs_pinned);
-        for (hipEvent_t e : s.ev_ring) if (e) (void)hipEventDestroy(e);
-        host_block_free(s.h_out, s.out_pinned);
-        if (s.h_small) isx_pin_free(s.h_small);
+        if (s.in.h_in) isx_pin_free(s.in.h_in);
+        host_block_free(s.in.h_runs, s.in.runs_pinned);
+        for (hipEvent_t e : s.in.ev_ring) if (e) (void)hipEventDestroy(e);
+        host_block_free(s.res.h_out, s.res.out_pinned);
+        if (s.res.h_small) isx_pin_free(s.res.h_small);
         t_pin += now_ms() - t_x;
-        for (hipEvent_t e : {s.ev_h2d0, s.ev_h2d1, s.ev_pass, s.ev_d2h0, s.ev_d2h1, s.ev_h2da, s.ev_h2db}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {s.in.ev_h2d0, s.in.ev_h2d1, s.res.ev_pass, s.res.ev_d2h0, s.res.ev_d2h1, s.in.ev_h2da, s.in.ev_h2db}) if (e) (void)hipEventDestroy(e);
     }
     if (pipe_timing)
         fprintf(stderr, "[isx_pipe_destroy] device tables %.1f ms, device arena %.1f ms, pinned staging %.1f ms, total %.1f ms\n", t_batch, t_dev, t_pin, now_ms() - t_f0);
@@ -378,7 +404,6 @@ static void pipe_free(isx_pipe *p)
         if (p->bounce_ev[i]) (void)hipEventDestroy(p->bounce_ev[i]);
     }
     if (p->s_h2d) (void)hipStreamDestroy(p->s_h2d);
-    if (p->s_h2d2) (void)hipStreamDestroy(p->s_h2d2);
     if (p->s_d2h) (void)hipStreamDestroy(p->s_d2h);
     if (p->s_fin) (void)hipStreamDestroy(p->s_fin);
     if (p->s_fin2) (void)hipStreamDestroy(p->s_fin2);
@@ -387,15 +412,14 @@ static void pipe_free(isx_pipe *p)
 }
 
 // device tables of a slot, sized for the pipe's capacities (the allocation half of isx_batch_create)
-static int slot_batch_create(isx_pipe *p, Slot &s, int index)
+static int slot_device_tables(isx_pipe *p, Slot &s, int index)
 {
     isx_ctx *c = p->ctx;
     const isx_params *prm = &p->prm;
-    const double t_s0 = now_ms();
     isx_batch *b = new isx_batch();
     s.b = b;
     b->ctx = c; b->prm = *prm; b->M = prm->n_mm_bins;
-    b->ps = getenv("ISX_ONE_PASS_QUEUE") ? 0 : (index & 1);
+    b->ps = index & 1;
     b->cap_pos = p->pp.max_pos; b->cap_obs = p->pp.max_obs; b->arena = true; b->ref_packed = 2;
     b->n_pos = p->pp.max_pos; b->n_obs = p->pp.max_obs;
     b->segs = p->segs; b->drec = p->drec;
@@ -482,297 +506,495 @@ static int slot_batch_create(isx_pipe *p, Slot &s, int index)
         b->cap_slev = b->cap_sites * (size_t)std::min(b->M, 8);
         HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&b->d_slev), b->cap_slev * sizeof(isx_slev)));
     }
-    // input arena: one layout for the pinned staging block and its device twin
+    return ISX_OK;
+}
+
+// the input arena's layout, one for the pinned staging block and its device twin; returns the bytes in front of the records
+static size_t input_arena_layout(const isx_pipe *p, SlotIn &in)
+{
+    const bool linkage = p->prm.enable_linkage != 0;
+    const int64_t cap_pos = p->pp.max_pos;
     size_t o = 0;
-    s.off_bounds = o; o = up(o + (size_t)(p->pp.max_splits + 1) * sizeof(int64_t));
-    s.off_win = o; o = up(o + ((size_t)cap_pos / 64 + 2) * sizeof(uint2));
-    s.off_ref = o; o = up(o + ref2_bytes(cap_pos) + refn_bytes(cap_pos));        // 2-bit plane | non-ACGT bit plane
-    s.off_gbase = o; o = up(o + ((size_t)(p->cap_rec / p->G) + ISX_TAIL_GROUPS) * sizeof(uint32_t));
-    s.off_ridx = o; if (prm->enable_linkage && !p->segs) o = up(o + ((size_t)p->cap_rec / ISX_CHUNK + 2) * sizeof(uint32_t));
-    s.off_pairs = o; if (prm->enable_linkage && p->segs && !p->drec) o = up(o + (size_t)p->cap_rec * sizeof(uint32_t));     // (reference-delta records carry the ids themselves)
-    s.off_rec = o;
-    s.in_bytes = up(o + (size_t)p->cap_rec * p->rb + ISX_TAIL_BYTES);
-    const size_t host_bytes = p->ring_half ? up(o + 2 * (size_t)p->ring_half * p->rb) : s.in_bytes;
+    in.off_bounds = o; o = up(o + (size_t)(p->pp.max_splits + 1) * sizeof(int64_t));
+    in.off_win = o; o = up(o + ((size_t)cap_pos / 64 + 2) * sizeof(uint2));
+    in.off_ref = o; o = up(o + ref2_bytes(cap_pos) + refn_bytes(cap_pos));        // 2-bit plane | non-ACGT bit plane
+    in.off_gbase = o; o = up(o + ((size_t)(p->cap_rec / p->G) + ISX_TAIL_GROUPS) * sizeof(uint32_t));
+    in.off_ridx = o; if (linkage && !p->segs) o = up(o + ((size_t)p->cap_rec / ISX_CHUNK + 2) * sizeof(uint32_t));
+    in.off_pairs = o; if (linkage && p->segs && !p->drec) o = up(o + (size_t)p->cap_rec * sizeof(uint32_t));     // (reference-delta records carry the ids themselves)
+    in.off_rec = o;
+    in.in_bytes = up(o + (size_t)p->cap_rec * p->rb + ISX_TAIL_BYTES);
+    return o;
+}
+
+// a slot's copy-in side: the pinned staging block and its device twin, the run tables, the ring's and the copy-in's events, the chunk directory
+static int slot_input_arena(isx_pipe *p, Slot &s, int index, double tables_ms)
+{
+    SlotIn &in = s.in;
+    const bool linkage = p->prm.enable_linkage != 0;
+    const size_t head = input_arena_layout(p, in);
+    const size_t host_bytes = p->ring_half ? up(head + 2 * (size_t)p->ring_half * p->rb) : in.in_bytes;
     const double t_a0 = now_ms();
-    HIP_TRY(isx_pin_malloc(reinterpret_cast<void **>(&s.h_in), host_bytes));
+    HIP_TRY(isx_pin_malloc(reinterpret_cast<void **>(&in.h_in), host_bytes));
     const double t_a1 = now_ms();
-    HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.d_in), s.in_bytes));
+    HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&in.d_in), in.in_bytes));
     if (pipe_timing)
         fprintf(stderr, "[isx_pipe_create] slot %d: device tables %.1f ms, pinned input %.1f MB %.1f ms, device arena %.1f MB %.1f ms\n", index,
-                t_a0 - t_s0, host_bytes / 1e6, t_a1 - t_a0, s.in_bytes / 1e6, now_ms() - t_a1);
-    if (prm->enable_linkage && !p->segs) {
+                tables_ms, host_bytes / 1e6, t_a1 - t_a0, in.in_bytes / 1e6, now_ms() - t_a1);
+    if (linkage && !p->segs) {
         // a read pair's records are consecutive: runs of tens to hundreds of records
-        s.cap_runs = (size_t)p->cap_rec / 64 + 4096;
-        s.runs_pinned = p->pp.depth > 1;
-        { const int hrc = host_block_alloc(reinterpret_cast<void **>(&s.h_runs), s.cap_runs * sizeof(isxenc::PairRun), s.runs_pinned); if (hrc != ISX_OK) return hrc; }
-        HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.d_runs), s.cap_runs * sizeof(uint2)));
+        in.cap_runs = (size_t)p->cap_rec / 64 + 4096;
+        in.runs_pinned = p->pp.depth > 1;
+        { const int hrc = host_block_alloc(reinterpret_cast<void **>(&in.h_runs), in.cap_runs * sizeof(isxenc::PairRun), in.runs_pinned); if (hrc != ISX_OK) return hrc; }
+        HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&in.d_runs), in.cap_runs * sizeof(uint2)));
     }
-    if (p->ring_half) for (hipEvent_t &e : s.ev_ring) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (prm->enable_linkage && p->rb == 4) HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.d_gpos16), (size_t)p->cap_rec * sizeof(uint16_t)));
-    // result blocks: a small pinned one (first SNV rows, first clonTR entries) and the position-sized arrays
-    o = 0;
-    s.o_snv = o; o = up(o + p->snv_prefix * sizeof(isx_snv));
-    s.o_rare = o; if (dense && prm->rarefied_coverage > 0) o = up(o + p->rare_prefix * sizeof(isx_rare));
-    s.small_bytes = o;
-    HIP_TRY(isx_pin_malloc(reinterpret_cast<void **>(&s.h_small), std::max<size_t>(s.small_bytes, 1)));
+    if (p->ring_half) for (hipEvent_t &e : in.ev_ring) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (linkage && p->rb == 4) HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&in.d_gpos16), (size_t)p->cap_rec * sizeof(uint16_t)));
+    for (hipEvent_t *e : {&in.ev_h2d0, &in.ev_h2d1, &in.ev_h2da, &in.ev_h2db}) HIP_TRY(hipEventCreate(e));
+    const size_t n_chunks = (size_t)(p->cap_rec / (p->segs ? (int64_t)p->G : (int64_t)ISX_CHUNK)) + 2;
+    in.cmin.resize(n_chunks); in.cmax.resize(n_chunks); in.cany.resize(n_chunks);
+    return ISX_OK;
+}
+
+// the two result blocks' layout: the small one (first SNV rows, first clonTR entries) and the position-sized arrays
+static void result_layout(const isx_pipe *p, const isx_batch *b, SlotOut &r)
+{
+    const bool dense = b->M == 1, rare = p->prm.rarefied_coverage > 0;
+    const size_t cap_pos = (size_t)p->pp.max_pos;
+    size_t o = 0;
+    r.o_snv = o; o = up(o + p->snv_prefix * sizeof(isx_snv));
+    r.o_rare = o; if (dense && rare) o = up(o + p->rare_prefix * sizeof(isx_rare));
+    r.small_bytes = o;
     o = 0;
     if (dense) {
-        s.o_cov16 = o; o = up(o + (size_t)cap_pos * 2);
-        s.o_clon = o; o = up(o + (size_t)cap_pos * 4);
+        r.o_cov16 = o; o = up(o + cap_pos * 2);
+        r.o_clon = o; o = up(o + cap_pos * 4);
         if (p->pp.want_counts) {
-            s.o_counts = o; o = up(o + (size_t)cap_pos * 16);
-            s.o_clonr = o; if (prm->rarefied_coverage > 0) o = up(o + (size_t)cap_pos * 4);
+            r.o_counts = o; o = up(o + cap_pos * 16);
+            r.o_clonr = o; if (rare) o = up(o + cap_pos * 4);
         }
     }
     if (b->lev_sparse) {
-        s.o_lmask = o; o = up(o + (size_t)cap_pos * b->lev_mask_bytes);
-        s.o_lwin = o; o = up(o + ((size_t)cap_pos / 64 + 2) * sizeof(uint32_t));
-        s.lcov_room = (size_t)cap_pos * (size_t)std::min(b->M, 4);
-        s.o_lcov = o; o = up(o + s.lcov_room);
-        s.lclon_room = (size_t)cap_pos;                                 // (cap_pos / 8 list entries)
-        s.o_lclon = o; o = up(o + s.lclon_room);
-        s.lrare_room = prm->rarefied_coverage > 0 ? (size_t)cap_pos / 2 : 0;
-        s.o_lrare = o; o = up(o + s.lrare_room);
+        r.o_lmask = o; o = up(o + cap_pos * b->lev_mask_bytes);
+        r.o_lwin = o; o = up(o + (cap_pos / 64 + 2) * sizeof(uint32_t));
+        r.lcov_room = cap_pos * (size_t)std::min(b->M, 4);
+        r.o_lcov = o; o = up(o + r.lcov_room);
+        r.lclon_room = cap_pos;                                         // (cap_pos / 8 list entries)
+        r.o_lclon = o; o = up(o + r.lclon_room);
+        r.lrare_room = rare ? cap_pos / 2 : 0;
+        r.o_lrare = o; o = up(o + r.lrare_room);
     }
-    s.out_bytes = o;
+    r.out_bytes = o;
+}
+
+// a slot's result side: the small block always pinned, the position-sized one pinned or plain; the pass's and the copy-out's events
+static int slot_result_blocks(isx_pipe *p, Slot &s, int index)
+{
+    SlotOut &r = s.res;
+    result_layout(p, s.b, r);
+    HIP_TRY(isx_pin_malloc(reinterpret_cast<void **>(&r.h_small), std::max<size_t>(r.small_bytes, 1)));
     const double t_o0 = now_ms();
     // Pinning (then unpinning) hundreds of MB costs more than moving them: 144 MB pinned = ~35 ms + ~30 ms to free.  A large
     // block lives in plain memory and the finisher moves the arrays there in pieces through two small pinned bounce buffers
     // (a hipMemcpyAsync straight into pageable memory crawls at < 2 GB/s and holds up every hipMalloc issued meanwhile).
     // A deep pipe (a long stream of batches) amortises the pinning and keeps its copy-out fully asynchronous.
-    s.out_pinned = s.out_bytes <= ((size_t)64 << 20) || p->pp.depth > 2;
-    { const int hrc = host_block_alloc(reinterpret_cast<void **>(&s.h_out), s.out_bytes, s.out_pinned); if (hrc != ISX_OK) return hrc; }
-    if (pipe_timing) fprintf(stderr, "[isx_pipe_create] slot %d: %s results %.1f MB %.1f ms\n", index, s.out_pinned ? "pinned" : "pageable", s.out_bytes / 1e6, now_ms() - t_o0);
-    for (hipEvent_t *e : {&s.ev_h2d0, &s.ev_h2d1, &s.ev_pass, &s.ev_d2h0, &s.ev_d2h1, &s.ev_h2da, &s.ev_h2db}) HIP_TRY(hipEventCreate(e));
-    const size_t n_chunks = (size_t)(p->cap_rec / (p->segs ? (int64_t)p->G : (int64_t)ISX_CHUNK)) + 2;
-    s.cmin.resize(n_chunks); s.cmax.resize(n_chunks); s.cany.resize(n_chunks);
+    r.out_pinned = r.out_bytes <= ((size_t)64 << 20) || p->pp.depth > 2;
+    { const int hrc = host_block_alloc(reinterpret_cast<void **>(&r.h_out), r.out_bytes, r.out_pinned); if (hrc != ISX_OK) return hrc; }
+    if (pipe_timing) fprintf(stderr, "[isx_pipe_create] slot %d: %s results %.1f MB %.1f ms\n", index, r.out_pinned ? "pinned" : "pageable", r.out_bytes / 1e6, now_ms() - t_o0);
+    for (hipEvent_t *e : {&r.ev_pass, &r.ev_d2h0, &r.ev_d2h1}) HIP_TRY(hipEventCreate(e));
+    return ISX_OK;
+}
+
+static int slot_create(isx_pipe *p, Slot &s, int index)
+{
+    const double t0 = now_ms();
+    int rc = slot_device_tables(p, s, index);
+    if (rc == ISX_OK) rc = slot_input_arena(p, s, index, now_ms() - t0);
+    if (rc == ISX_OK) rc = slot_result_blocks(p, s, index);
+    return rc;
+}
+
+// ---- the form a batch's tables travel home in ----
+// The form a pass is asked for (PassForm, isx_batch.h) is picked here, revised here after a pass, and what then came home is said here
+// (LandedForm): these three functions are all that decides it.  launch_pass turns the PassForm into kernel arguments, the output lists
+// below into copies, isx_pipe_collect the LandedForm into the caller's pointers.
+
+// What a pass hands back depends on the batch's mean depth (n_obs / n_pos); a staged and a submitted batch must come to the same form
+// (the tests compare them byte for byte), so the cuts live here alone.
+constexpr double COV8_BELOW_DEPTH = 16.0;       // coverage travels in one byte a position
+constexpr double NIB_BELOW_DEPTH = 6.0;         // lean slots: ... in four bits (most windows stay within them)
+constexpr double LEV_COV8_BELOW_DEPTH = 64.0;   // level-sparse slots: a level's coverage in one byte (the few values >= 255 travel in a list)
+constexpr double RARE_DENSE_OBS_FACTOR = 4.0;   // lean slots: the clonTR table goes back dense once n_obs * 4 >= rarefied_coverage * n_pos
+
+static PassForm form_for_depth(const isx_batch *b, int rarefied_coverage)
+{
+    const double n_obs = (double)b->n_obs, n_pos = (double)b->n_pos;
+    PassForm f;
+    // without a count table to hand back, the position-sized tables travel shrunk: clonality as the list of values other than 1.0,
+    // coverage in one byte for a shallow batch
+    f.sparse_out = b->M == 1 && b->d_clon_list != nullptr;
+    f.cov8_out = f.sparse_out && n_obs < COV8_BELOW_DEPTH * n_pos;
+    f.nib_out = f.cov8_out && b->lean && n_obs < NIB_BELOW_DEPTH * n_pos;
+    f.rare_dense = !(b->lean && f.sparse_out) || n_obs * RARE_DENSE_OBS_FACTOR >= (double)rarefied_coverage * n_pos;
+    if (b->lev_sparse) f.lev_cov_bytes = n_obs < LEV_COV8_BELOW_DEPTH * n_pos ? 1 : 2;
+    return f;
+}
+
+// After a pass whose tables all fitted (sizes read, no capacity flag): did the form hold?  If not it is revised here and the pass has to be
+// repeated.  *grow_lists: a level-sparse slot's lists outgrew their tables (the form stays, the tables grow).
+static bool form_revise(const isx_pipe *p, isx_batch *b, bool *grow_lists)
+{
+    PassForm &f = b->form;
+    const bool dense = b->M == 1, rare = p->prm.rarefied_coverage > 0;
+    const size_t n_pos = (size_t)b->n_pos, n_clon = b->n_clon, n_rare = b->n_rare, n_sat = b->n_sat;
+    // a batch taken for shallow that has more positions beyond 255 than the exact-coverage list holds: again with 16 bits
+    const bool cov8_overflow = dense && f.sparse_out && f.cov8_out && !f.nib_pass && n_sat > b->cap_sat;
+    // a 4-bit plane whose 16-bit rows would not fit the slot's coverage block (most windows beyond 15: not a shallow batch after all)
+    const bool nib_overflow = dense && f.nib_pass && (n_pos / 2 + 128 + (size_t)b->n_cov_rows * (size_t)b->W * 2 > n_pos * 2 ||
+                                                      ((size_t)b->n_cov_rows + 1) * (size_t)b->W > (size_t)(b->cap_pos ? b->cap_pos : b->n_pos));
+    // a lean slot whose clonality list cannot be used (too many entries for the list / for a list to pay): again, with the dense array
+    const bool clon_overflow = dense && f.sparse_out && b->lean && !f.clon_dense && (n_clon > b->cap_clon || n_clon * 2 > n_pos);
+    // a lean slot's batch taken for shallow whose clonTR list cannot be used (deep after all): again, with the dense array
+    const bool rare_overflow = dense && rare && !f.rare_dense && (n_rare > p->cap_rare || n_rare * 8 > n_pos);
+    // level-sparse mm slot: a list that outgrew its table (the kernel wrote what fitted; the cursors say what there was)
+    *grow_lists = b->lev_sparse && (n_clon > b->cap_clon || n_sat > b->cap_sat || (rare && n_rare > b->cap_rare));
+    if (cov8_overflow) f.cov8_out = false;
+    if (nib_overflow) f.nib_out = false;
+    if (clon_overflow) f.clon_dense = true;
+    if (rare_overflow) f.rare_dense = true;
+    return cov8_overflow || nib_overflow || clon_overflow || rare_overflow || *grow_lists;
+}
+
+// What the finisher brings home of a settled pass.  A list goes back as the array where it overflowed its table or is no smaller than the
+// array (a plain slot's pass wrote both); a lean slot's pass wrote the array only after form_revise asked for it, on the same conditions.
+static LandedForm form_landed(const isx_pipe *p, const isx_batch *b)
+{
+    const PassForm &f = b->form;
+    const size_t n_pos = (size_t)b->n_pos;
+    LandedForm l;
+    l.lev_cov_bytes = f.lev_cov_bytes;
+    if (b->M != 1) return l;
+    l.sat_complete = (size_t)b->n_sat <= b->cap_sat;
+    if (f.sparse_out) {
+        l.cov4 = f.nib_pass;
+        l.cov8 = f.cov8_out && !f.nib_pass;
+        if (l.cov4) { l.cov_window = b->W; l.cov_rows_off = ((n_pos + 1) / 2 + 63) & ~(size_t)63; }
+        l.clon_sparse = (size_t)b->n_clon <= b->cap_clon && (size_t)b->n_clon * 2 <= n_pos;
+    }
+    // a deep sample: most positions reach the rarefied coverage, so the 8-byte list is no smaller than the 4-byte array (and would need
+    // sorting) -- or the device list overflowed
+    l.rare_dense = p->prm.rarefied_coverage > 0 && ((size_t)b->n_rare > p->cap_rare || (size_t)b->n_rare * 8 > n_pos);
+    return l;
+}
+
+// ---- the position-sized outputs: what goes where in h_out.  The eager copy-out of a pass, the finisher's fetch and the byte count walk these ----
+struct OutPiece { size_t off; const void *src; size_t bytes; };         // `bytes` at `src` on the device -> h_out + off
+
+// a dense batch's tables in the form `l` (a slot with a count table: always the full tables, known before the pass has run); returns how many
+static int dense_out_pieces(const isx_pipe *p, const Slot &s, const LandedForm &l, OutPiece o[4])
+{
+    const isx_batch *b = s.b;
+    const SlotOut &r = s.res;
+    const size_t n_pos = (size_t)b->n_pos;
+    int n = 0;
+    if (!b->form.sparse_out) {
+        o[n++] = {r.o_cov16, b->d_cov16, n_pos * 2};
+        o[n++] = {r.o_clon, b->d_clon, n_pos * 4};
+        if (p->pp.want_counts) {
+            o[n++] = {r.o_counts, b->d_counts, n_pos * 16};
+            if (p->prm.rarefied_coverage > 0) o[n++] = {r.o_clonr, b->d_clon_r, n_pos * 4};
+        }
+        return n;
+    }
+    // coverage in 2 bytes, or 1 for a shallow batch (exact values of the few positions at 255 / 65535 or beyond in sat_rows), or
+    // min(coverage, 15) of two positions a byte + the windows that hold anything beyond 15 as whole 16-bit rows
+    if (l.cov4) {
+        o[n++] = {r.o_cov16, b->d_cov8, (n_pos + 1) / 2};
+        o[n++] = {r.o_cov16 + l.cov_rows_off, b->d_cov16, (size_t)b->n_cov_rows * (size_t)b->W * 2};
+    } else if (l.cov8) o[n++] = {r.o_cov16, b->d_cov8, n_pos};
+    else o[n++] = {r.o_cov16, b->d_cov16, n_pos * 2};
+    // clonality: a position that reaches min_cov has exactly 1.0 unless more than one base was observed there -- only those exceptions
+    // travel, as a (position, value) list sorted by position on the device
+    if (l.clon_sparse) o[n++] = {r.o_clon, b->d_clon_sorted, (size_t)b->n_clon * sizeof(isx_rare)};
+    else o[n++] = {r.o_clon, b->d_clon, n_pos * 4};
+    return n;
+}
+
+// a level-sparse batch's: the level mask | the windows' first level indices | one coverage byte (or two) per present level | the clonality
+// list | the clonTR list.  The last three have rooms in h_out that a deep sample outgrows (fetch_level_tables).
+static void lev_out_pieces(const isx_pipe *p, const Slot &s, OutPiece o[5])
+{
+    const isx_batch *b = s.b;
+    const SlotOut &r = s.res;
+    o[0] = {r.o_lmask, b->d_lev_mask, (size_t)b->n_pos * b->lev_mask_bytes};
+    o[1] = {r.o_lwin, b->d_lev_win_off, (size_t)b->n_win * sizeof(uint32_t)};
+    o[2] = {r.o_lcov, b->d_lev_cov, (size_t)b->sizes.n_entries * (size_t)b->form.lev_cov_bytes};
+    o[3] = {r.o_lclon, b->d_clon_list, (size_t)b->n_clon * sizeof(isx_rare)};
+    o[4] = {r.o_lrare, b->d_rare, p->prm.rarefied_coverage > 0 ? (size_t)b->n_rare * sizeof(isx_rare) : 0};
+}
+
+// the bytes a finished batch brought home (isx_pipe_result.d2h_bytes): the counted row prefixes, the lists above, the small read-backs that scale
+static int64_t slot_d2h_bytes(const isx_pipe *p, const Slot &s)
+{
+    const isx_batch *b = s.b;
+    const SlotOut &r = s.res;
+    size_t sum = std::min((size_t)b->sizes.n_snv, p->snv_prefix) * sizeof(isx_snv);
+    if (b->M == 1) {
+        if (p->prm.rarefied_coverage > 0) sum += std::min((size_t)b->n_rare, p->rare_prefix) * sizeof(isx_rare);
+        OutPiece o[4];
+        int n = dense_out_pieces(p, s, r.landed, o);
+        // (a plain result block has never counted its count table and clonTR array; kept, the figure is compared from version to version)
+        if (!b->form.sparse_out && !r.out_pinned) n = std::min(n, 2);
+        for (int i = 0; i < n; i++) sum += o[i].bytes;
+        if (r.landed.cov4) sum += (size_t)b->n_cov_rows * sizeof(uint32_t);
+    }
+    if (b->lev_sparse) {
+        OutPiece o[5];
+        lev_out_pieces(p, s, o);
+        for (const OutPiece &q : o) sum += q.bytes;
+        sum += r.sat_rows.size() * sizeof(isx_sat);
+    }
+    return (int64_t)sum;
+}
+
+// device -> the slot's result block: through the bounce buffers into a plain block, enqueued on the finisher's queue into a pinned one
+static int fetch_block(isx_pipe *p, const Slot &s, void *hdst, const void *dsrc, size_t bytes, hipStream_t sfin)
+{
+    if (!bytes) return ISX_OK;
+    if (!s.res.out_pinned) return bounce_d2h(p, hdst, dsrc, bytes, sfin);
+    HIP_TRY(isx_copy_to_host(hdst, dsrc, bytes, sfin));
+    return ISX_OK;
+}
+
+// device -> plain host memory outside the block (a *_big vector), waited for: through the bounce buffers if the pipe has any, else a blocking copy
+static int fetch_plain(isx_pipe *p, void *hdst, const void *dsrc, size_t bytes, hipStream_t sfin)
+{
+    if (p->bounce[0]) return bounce_d2h(p, hdst, dsrc, bytes, sfin);
+    HIP_TRY(hipMemcpy(hdst, dsrc, bytes, hipMemcpyDeviceToHost));
+    return ISX_OK;
+}
+
+// small tables into any host memory, waited for: through the calling thread's pinned scratch (isx_read_back), not the DMA queue
+static int pull(void *hdst, const void *dsrc, size_t bytes, hipStream_t sfin)
+{
+    if (!bytes) return ISX_OK;
+    HIP_TRY(isx_read_back(hdst, dsrc, bytes, sfin));
+    HIP_TRY(isx_read_sync(sfin));
+    return ISX_OK;
+}
+
+// a level-sparse slot's list table that a batch outgrew: what the batch needs and a quarter (the pass queue must be done with the old table)
+static int grow_list(uint2 **lp, size_t *cap, size_t need, hipStream_t ps)
+{
+    if (need <= *cap) return ISX_OK;
+    HIP_TRY(isx_wait_stream(ps));
+    if (*lp) isx_dev_free(*lp);
+    *lp = nullptr;
+    const size_t want = need + need / 4 + 65536;
+    HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(lp), want * sizeof(uint2)));
+    *cap = want;
+    return ISX_OK;
+}
+
+// ---- finishing a batch: the stages of finish_slot, in its order ----
+struct Finish {
+    isx_pipe *p; Slot &s; isx_batch *b;
+    hipStream_t sfin, ps;               // this finisher's queue; the batch's pass queue
+    bool redo = false;                  // the pass was repeated: the tables that left behind the first one are fetched again
+};
+
+// Settle the pass: sizes from the published cursors; a table that was too small is grown, a form that did not hold is revised, and the pass
+// repeated (the slot still holds its input) -- at most 8 times.
+static int settle_pass(Finish &f)
+{
+    isx_pipe *p = f.p;
+    isx_batch *b = f.b;
+    isx_ctx *c = p->ctx;
+    const bool dense = b->M == 1, rare = p->prm.rarefied_coverage > 0;
+    for (int attempt = 0;; attempt++) {
+        uint32_t cf = 0;
+        int rc = finish_pass_sizes(b, &cf, f.sfin);     // (the linkage stages follow the fetches: one wait for both)
+        if (rc != ISX_OK) return rc;
+        bool grow_lists = false;
+        if (!cf && !form_revise(p, b, &grow_lists)) return ISX_OK;
+        if (attempt == 7) { isx_set_error("output tables still too small after 8 growth steps"); return ISX_ERR_CAPACITY; }
+        if (cf && (rc = batch_grow_tables(b, cf)) != ISX_OK) return rc;
+        if (grow_lists) {
+            if ((rc = grow_list(&b->d_clon_list, &b->cap_clon, b->n_clon, f.ps)) != ISX_OK) return rc;
+            if ((rc = grow_list(&b->d_sat, &b->cap_sat, b->n_sat, f.ps)) != ISX_OK) return rc;
+            if (rare && (rc = grow_list(&b->d_rare, &b->cap_rare, b->n_rare, f.ps)) != ISX_OK) return rc;
+        }
+        if (!dense && !b->lev_sparse) b->cap_ovf = b->cap_entries - (size_t)b->n_win * b->slab;
+        std::lock_guard<std::mutex> lk(p->launch_mu);
+        if (dense && rare && b->form.rare_dense)
+            HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->d_clon_r), 0x7FC00000, (size_t)b->n_pos, f.ps));
+        if ((rc = launch_pass(b)) != ISX_OK) return rc;
+        {   // published here, under the launch lock like a submit's pass: finish_pass must not touch the stream's publication state
+            PileupArgs pa{};
+            pa.cursors = b->d_cursors; pa.host_state = b->d_host_state;
+            launch_publish_state(pa, b->epoch, f.ps);
+            b->publish_enqueued = true;
+            if (c->unpublished[b->ps] == b) c->unpublished[b->ps] = nullptr;
+        }
+        f.redo = true;
+    }
+}
+
+// The dense tables.  A shrunk batch's, a plain result block's, or those that predate a repeated pass: the others left behind the pass
+// itself (enqueue_pass_impl).
+static int fetch_dense_tables(Finish &f)
+{
+    isx_batch *b = f.b;
+    SlotOut &r = f.s.res;
+    const LandedForm &l = r.landed;
+    int rc = ISX_OK;
+    if (f.redo) HIP_TRY(isx_wait_stream(f.ps));
+    if (b->form.sparse_out || !r.out_pinned || f.redo) {
+        OutPiece o[4];
+        const int n = dense_out_pieces(f.p, f.s, l, o);
+        for (int i = 0; i < n; i++) {
+            // the clonality list is sorted right in front of its copy (b->ordered: k_win_gather already wrote it in position order behind the pileup kernel)
+            if (l.clon_sparse && o[i].src == b->d_clon_sorted && !b->ordered &&
+                (rc = sort_pairs_by_position(f.sfin, b->d_clon_list, b->d_clon_sorted, (size_t)b->n_clon, &r.sort_temp, &r.sort_temp_bytes)) != ISX_OK) return rc;
+            if ((rc = fetch_block(f.p, f.s, r.h_out + o[i].off, o[i].src, o[i].bytes, f.sfin)) != ISX_OK) return rc;
+        }
+    }
+    if (l.cov4) {
+        r.cov_row_win.resize(b->n_cov_rows);
+        if (b->n_cov_rows && isx_read_back(r.cov_row_win.data(), b->d_cov_row_win, (size_t)b->n_cov_rows * sizeof(uint32_t), f.sfin) != hipSuccess) {
+            isx_set_error("isx_pipe finisher: read-back of the coverage rows' windows"); isx_read_drop(); return ISX_ERR_HIP;
+        }
+    }
+    // exact coverage of the saturated positions (a handful; none at all for most batches)
+    r.sat_rows.resize(l.sat_complete ? (size_t)b->n_sat : 0);
+    if (!r.sat_rows.empty()) HIP_TRY(isx_read_back(r.sat_rows.data(), b->d_sat, r.sat_rows.size() * sizeof(isx_sat), f.sfin));
+    return ISX_OK;      // (no wait here: the linkage stages end with the one wait that also covers these copies)
+}
+
+// The level tables (mm profiling on).
+static int fetch_level_tables(Finish &f)
+{
+    isx_pipe *p = f.p;
+    isx_batch *b = f.b;
+    SlotOut &r = f.s.res;
+    int rc = ISX_OK;
+    if (f.redo) HIP_TRY(isx_wait_stream(f.ps));
+    OutPiece o[5];
+    lev_out_pieces(p, f.s, o);
+    // a small batch's tables (a C2 batch: 5 + 12 MB) leave by copy kernel, not by DMA: see isx_copy_to_host_route
+    const bool by_kernel = r.out_pinned && o[0].bytes + o[2].bytes + o[3].bytes + o[4].bytes <= LEV_KERNEL_MAX;
+    std::vector<isx_copy_job> jobs;                             // (by_kernel: all of the batch's tables in one launch)
+    auto fetch_lev = [&](const OutPiece &q) -> int {
+        void *hdst = r.h_out + q.off;
+        if (!by_kernel || ((reinterpret_cast<uintptr_t>(hdst) | reinterpret_cast<uintptr_t>(q.src)) & 15)) return fetch_block(p, f.s, hdst, q.src, q.bytes, f.sfin);
+        jobs.push_back(isx_copy_job{hdst, q.src, q.bytes});
+        return ISX_OK;
+    };
+    // what outgrows its pinned room (a deep sample's clonTR list, a coverage stream of more than four levels a position): plain vectors
+    auto fetch_or_big = [&](const OutPiece &q, size_t room, auto &big) -> int {
+        big.clear();
+        if (q.bytes <= room) return fetch_lev(q);
+        big.resize((q.bytes + sizeof(big[0]) - 1) / sizeof(big[0]));
+        return fetch_plain(p, big.data(), q.src, q.bytes, f.sfin);
+    };
+    if ((rc = fetch_lev(o[0])) != ISX_OK || (rc = fetch_lev(o[1])) != ISX_OK) return rc;
+    if ((rc = fetch_or_big(o[2], r.lcov_room, r.lcov_big)) != ISX_OK) return rc;
+    if ((rc = fetch_or_big(o[3], r.lclon_room, r.lclon_big)) != ISX_OK) return rc;
+    if (o[4].bytes && (rc = fetch_or_big(o[4], r.lrare_room, r.lrare_big)) != ISX_OK) return rc;
+    if (!jobs.empty()) HIP_TRY(isx_copy_multi_to_host(jobs.data(), (int)jobs.size(), f.sfin));
+    r.sat_rows.resize((size_t)b->n_sat);
+    if (!r.sat_rows.empty()) HIP_TRY(isx_read_back(r.sat_rows.data(), b->d_sat, r.sat_rows.size() * sizeof(isx_sat), f.sfin));
+    return ISX_OK;      // (no wait here either)
+}
+
+// The linkage stages, on this finisher's queue behind the copies above; the bucket chain's one read-back is the wait for all of it.
+static int link_and_wait(Finish &f)
+{
+    const int rc = finish_pass_link(f.b, f.sfin);
+    if (rc != ISX_OK) return rc;
+    if (!(f.p->prm.enable_linkage && f.b->link_chain == 3)) HIP_TRY(isx_read_sync(f.sfin));
+    return ISX_OK;
+}
+
+// The clonTR table of a dense batch: the sparse list in ascending positions, or the dense array (LandedForm::rare_dense).
+static int fetch_rare_table(Finish &f)
+{
+    isx_pipe *p = f.p;
+    isx_batch *b = f.b;
+    SlotOut &r = f.s.res;
+    const size_t n_rare = b->n_rare;
+    r.rare_big.clear();
+    if (r.landed.rare_dense) {
+        // with a count table the array has a place in the result block and came home with the dense tables; without one there is no
+        // pinned room for it (deep samples are the exception, pinning 4 more bytes per position for every pipe is not worth it)
+        if (p->pp.want_counts) return ISX_OK;
+        if (r.clonr_big.size() < (size_t)b->n_pos) r.clonr_big.resize((size_t)b->n_pos);
+        return fetch_plain(p, r.clonr_big.data(), b->d_clon_r, (size_t)b->n_pos * 4, f.sfin);
+    }
+    isx_rare *rr = reinterpret_cast<isx_rare *>(r.h_small + r.o_rare);
+    if (n_rare > p->rare_prefix || f.redo) {
+        if (n_rare > p->rare_prefix) { r.rare_big.resize(n_rare); rr = r.rare_big.data(); }
+        const int rc = pull(rr, b->d_rare, n_rare * sizeof(isx_rare), f.sfin);
+        if (rc != ISX_OK) return rc;
+    }
+    if (!b->ordered) std::sort(rr, rr + n_rare, [](const isx_rare &x, const isx_rare &y) { return x.gpos < y.gpos; });
+    return ISX_OK;
+}
+
+// The SNV rows in (position, mm) order, the LD rows, and the checksum over both.
+static int fetch_rows(Finish &f)
+{
+    isx_pipe *p = f.p;
+    isx_batch *b = f.b;
+    SlotOut &r = f.s.res;
+    const bool linkage = p->prm.enable_linkage != 0;
+    const size_t n_snv = (size_t)b->sizes.n_snv;
+    isx_snv *rows = reinterpret_cast<isx_snv *>(r.h_small + r.o_snv);
+    if (n_snv > p->snv_prefix || f.redo) {
+        if (n_snv > p->snv_prefix) { r.snv_big.resize(n_snv); rows = r.snv_big.data(); }
+        const int rc = pull(rows, b->d_snv, n_snv * sizeof(isx_snv), f.sfin);
+        if (rc != ISX_OK) return rc;
+    }
+    if (!b->ordered) std::sort(rows, rows + n_snv, [](const isx_snv &x, const isx_snv &y) { return x.gpos != y.gpos ? x.gpos < y.gpos : x.mm < y.mm; });
+    if (linkage) {
+        // the LD rows too: a blocking copy issued by the caller would queue behind the next batches' large transfers
+        r.ld_rows.resize((size_t)b->sizes.n_ld);
+        if (!r.ld_rows.empty() && b->ld_host && r.ld_rows.size() <= b->n_ld_host) memcpy(r.ld_rows.data(), b->ld_host, r.ld_rows.size() * sizeof(isx_ld));   // came home with the chain's state words
+        else if (!r.ld_rows.empty()) { const int rc = pull(r.ld_rows.data(), b->L.ld.p, r.ld_rows.size() * sizeof(isx_ld), f.sfin); if (rc != ISX_OK) return rc; }
+    }
+    r.rows_checksum = bytes_checksum(r.ld_rows.data(), linkage ? r.ld_rows.size() * sizeof(isx_ld) : 0, bytes_checksum(rows, n_snv * sizeof(isx_snv), 0));
     return ISX_OK;
 }
 
 // everything between "the batch's copy-out has landed" and "its tables can be handed to the caller"
 static int finish_slot(isx_pipe *p, Slot &s, hipStream_t sfin)
 {
-    isx_ctx *c = p->ctx;
     isx_batch *b = s.b;
+    SlotOut &r = s.res;
     const bool dense = b->M == 1;
     const double t0 = now_ms();
-    HIP_TRY(isx_wait_event(s.ev_d2h1));
-    s.finish_wait_ms = (float)(now_ms() - t0);
+    HIP_TRY(isx_wait_event(r.ev_d2h1));
+    r.finish_wait_ms = (float)(now_ms() - t0);
     const double t_c0 = now_ms();
-    double t_fin = 0, t_rare = 0;
-    hipStream_t ps = c->pstream[b->ps];
-    bool redo = false;
-    for (int attempt = 0;; attempt++) {
-        uint32_t cf = 0;
-        int rc = finish_pass_sizes(b, &cf, sfin);     // sizes from the published cursors (the linkage stages follow the fetches below: one wait for both)
-        if (rc != ISX_OK) return rc;
-        // a batch taken for shallow that has more positions beyond 255 than the exact-coverage list holds: again with 16 bits
-        const bool cov8_overflow = !cf && dense && b->sparse_out && b->cov8_out && !b->nib_pass && (size_t)b->n_sat > b->cap_sat;
-        // a 4-bit plane whose 16-bit rows would not fit the slot's coverage block (most windows beyond 15: not a shallow batch after all)
-        const bool nib_overflow = !cf && dense && b->nib_pass &&
-                                  ((size_t)b->n_pos / 2 + 128 + (size_t)b->n_cov_rows * (size_t)b->W * 2 > (size_t)b->n_pos * 2 ||
-                                   ((size_t)b->n_cov_rows + 1) * (size_t)b->W > (size_t)(b->cap_pos ? b->cap_pos : b->n_pos));
-        // a lean slot whose clonality list cannot be used (too many entries for the list / for a list to pay): again, with the dense array
-        const bool clon_overflow = !cf && dense && b->sparse_out && b->lean && !b->clon_dense &&
-                                   ((size_t)b->n_clon > b->cap_clon || (size_t)b->n_clon * 2 > (size_t)b->n_pos);
-        // a lean slot's batch taken for shallow whose clonTR list cannot be used (deep after all): again, with the dense array
-        const bool rare_overflow = !cf && dense && p->prm.rarefied_coverage > 0 && !b->rare_dense &&
-                                   ((size_t)b->n_rare > p->cap_rare || (size_t)b->n_rare * 8 > (size_t)b->n_pos);
-        // level-sparse mm slot: a list that outgrew its table (the kernel wrote what fitted; the cursors say what there was)
-        const bool lev_overflow = !cf && b->lev_sparse && ((size_t)b->n_clon > b->cap_clon || (size_t)b->n_sat > b->cap_sat ||
-                                                           (p->prm.rarefied_coverage > 0 && (size_t)b->n_rare > b->cap_rare));
-        if (!cf && !cov8_overflow && !clon_overflow && !nib_overflow && !rare_overflow && !lev_overflow) break;
-        if (attempt == 7) { isx_set_error("output tables still too small after 8 growth steps"); return ISX_ERR_CAPACITY; }
-        // a table was too small for this batch: grow it and repeat the pass (the slot still holds its input)
-        if (cov8_overflow) b->cov8_out = false;
-        if (nib_overflow) b->nib_out = false;
-        if (clon_overflow) b->clon_dense = true;
-        if (rare_overflow) b->rare_dense = true;
-        if (cf && (rc = batch_grow_tables(b, cf)) != ISX_OK) return rc;
-        if (lev_overflow) {
-            auto regrow_list = [&](uint2 **lp, size_t *cap, size_t need) -> int {
-                if (need <= *cap) return ISX_OK;
-                HIP_TRY(isx_wait_stream(ps));
-                if (*lp) isx_dev_free(*lp);
-                *lp = nullptr;
-                const size_t want = need + need / 4 + 65536;
-                HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(lp), want * sizeof(uint2)));
-                *cap = want;
-                return ISX_OK;
-            };
-            if ((rc = regrow_list(&b->d_clon_list, &b->cap_clon, b->n_clon)) != ISX_OK) return rc;
-            if ((rc = regrow_list(&b->d_sat, &b->cap_sat, b->n_sat)) != ISX_OK) return rc;
-            if (p->prm.rarefied_coverage > 0 && (rc = regrow_list(&b->d_rare, &b->cap_rare, b->n_rare)) != ISX_OK) return rc;
-        }
-        if (!dense && !b->lev_sparse) b->cap_ovf = b->cap_entries - (size_t)b->n_win * b->slab;
-        std::lock_guard<std::mutex> lk(p->launch_mu);
-        if (dense && p->prm.rarefied_coverage > 0 && b->rare_dense)
-            HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->d_clon_r), 0x7FC00000, (size_t)b->n_pos, ps));
-        if ((rc = launch_pass(b)) != ISX_OK) return rc;
-        {   // published here, under the launch lock like a submit's pass: finish_pass must not touch the stream's publication state
-            PileupArgs pa{};
-            pa.cursors = b->d_cursors; pa.host_state = b->d_host_state;
-            launch_publish_state(pa, b->epoch, ps);
-            b->publish_enqueued = true;
-            if (c->unpublished[b->ps] == b) c->unpublished[b->ps] = nullptr;
-        }
-        redo = true;
-    }
-    s.d2h_bytes += (int64_t)(std::min((size_t)b->sizes.n_snv, p->snv_prefix) * sizeof(isx_snv));
-    if (dense && p->prm.rarefied_coverage > 0) s.d2h_bytes += (int64_t)(std::min((size_t)b->n_rare, p->rare_prefix) * sizeof(isx_rare));
-    // device -> the slot's result block: through the bounce buffers into a plain block, a blocking copy into a pinned one
-    // small tables into any host memory, waited for: through the calling thread's pinned scratch (isx_read_back), not the DMA queue
-    auto pull = [&](void *hdst, const void *dsrc, size_t bytes) -> int {
-        if (!bytes) return ISX_OK;
-        HIP_TRY(isx_read_back(hdst, dsrc, bytes, sfin));
-        HIP_TRY(isx_read_sync(sfin));
-        return ISX_OK;
-    };
+    Finish f{p, s, b, sfin, p->ctx->pstream[b->ps]};
+    int rc = settle_pass(f);
+    if (rc != ISX_OK) return rc;
+    r.landed = form_landed(p, b);
     // the small read-backs from here on (window lists, exact-coverage rows, the linkage stages' state words + rows) leave in ONE copy launch, made
     // by the wait that delivers them: nothing writes their sources in between
     // (an exit with read-backs still pending -- an error between a read-back and its wait -- forgets them: their destinations may not outlive this call)
     struct ReadBatch { ReadBatch() { isx_read_batch(true); } ~ReadBatch() { isx_read_drop(); } } read_batch;
-    auto fetch = [&](void *hdst, const void *dsrc, size_t bytes) -> int {
-        if (!bytes) return ISX_OK;
-        if (!s.out_pinned) return bounce_d2h(p, hdst, dsrc, bytes, sfin);
-        HIP_TRY(isx_copy_to_host(hdst, dsrc, bytes, sfin));
-        return ISX_OK;
-    };
-    if (dense) {
-        int rc = ISX_OK;
-        if (redo) HIP_TRY(isx_wait_stream(ps));
-        s.cov8 = false; s.cov4 = false; s.clon_sparse = false; s.sat_complete = (size_t)b->n_sat <= b->cap_sat;
-        if (b->sparse_out) {
-            // coverage in 2 bytes, or 1 for a shallow batch (exact values of the few positions at 255 / 65535 or beyond in the
-            // list below); clonality: a position that reaches min_cov has exactly 1.0 unless more than one base was observed there
-            // -- only those exceptions travel, as a (position, value) list sorted by position on the device
-            s.cov8 = b->cov8_out && !b->nib_pass;
-            if (b->nib_pass) {
-                // min(coverage, 15) of two positions a byte + the windows that hold anything beyond 15 as whole 16-bit rows
-                const size_t nib_bytes = ((size_t)b->n_pos + 1) / 2, rows_bytes = (size_t)b->n_cov_rows * (size_t)b->W * 2;
-                s.cov4 = true; s.cov_window = b->W;
-                s.cov_rows_off = (nib_bytes + 63) & ~(size_t)63;
-                rc = fetch(s.h_out + s.o_cov16, b->d_cov8, nib_bytes);
-                if (rc == ISX_OK) rc = fetch(s.h_out + s.o_cov16 + s.cov_rows_off, b->d_cov16, rows_bytes);
-                s.cov_row_win.resize(b->n_cov_rows);
-                if (rc == ISX_OK && b->n_cov_rows && isx_read_back(s.cov_row_win.data(), b->d_cov_row_win, (size_t)b->n_cov_rows * sizeof(uint32_t), sfin) != hipSuccess) {
-                    isx_set_error("isx_pipe finisher: read-back of the coverage rows' windows"); isx_read_drop(); rc = ISX_ERR_HIP;
-                }
-                s.d2h_bytes += (int64_t)(nib_bytes + rows_bytes + (size_t)b->n_cov_rows * 4);
-            } else if (s.cov8) rc = fetch(s.h_out + s.o_cov16, b->d_cov8, (size_t)b->n_pos);
-            else rc = fetch(s.h_out + s.o_cov16, b->d_cov16, (size_t)b->n_pos * 2);
-            if (rc != ISX_OK) return rc;
-            if (!s.cov4) s.d2h_bytes += (int64_t)b->n_pos * (s.cov8 ? 1 : 2);
-            const size_t n_clon = b->n_clon;
-            if (n_clon <= b->cap_clon && n_clon * 2 <= (size_t)b->n_pos) {
-                // (b->ordered: k_win_gather already wrote the list in position order behind the pileup kernel)
-                if (!b->ordered && (rc = sort_pairs_by_position(sfin, b->d_clon_list, b->d_clon_sorted, n_clon, &s.sort_temp, &s.sort_temp_bytes)) != ISX_OK) return rc;
-                if ((rc = fetch(s.h_out + s.o_clon, b->d_clon_sorted, n_clon * sizeof(isx_rare))) != ISX_OK) return rc;
-                s.clon_sparse = true;
-                s.d2h_bytes += (int64_t)(n_clon * sizeof(isx_rare));
-            } else {
-                if ((rc = fetch(s.h_out + s.o_clon, b->d_clon, (size_t)b->n_pos * 4)) != ISX_OK) return rc;
-                s.d2h_bytes += (int64_t)b->n_pos * 4;
-            }
-        } else if (!s.out_pinned || redo) {     // a plain result block, or tables that predate the repeated pass
-            if ((rc = fetch(s.h_out + s.o_cov16, b->d_cov16, (size_t)b->n_pos * 2)) != ISX_OK) return rc;
-            if ((rc = fetch(s.h_out + s.o_clon, b->d_clon, (size_t)b->n_pos * 4)) != ISX_OK) return rc;
-            if (p->pp.want_counts) {
-                if ((rc = fetch(s.h_out + s.o_counts, b->d_counts, (size_t)b->n_pos * 16)) != ISX_OK) return rc;
-                if (p->prm.rarefied_coverage > 0 && (rc = fetch(s.h_out + s.o_clonr, b->d_clon_r, (size_t)b->n_pos * 4)) != ISX_OK) return rc;
-            }
-        }
-        // exact coverage of the saturated positions (a handful; none at all for most batches)
-        s.sat_rows.resize(s.sat_complete ? (size_t)b->n_sat : 0);
-        if (!s.sat_rows.empty()) HIP_TRY(isx_read_back(s.sat_rows.data(), b->d_sat, s.sat_rows.size() * sizeof(isx_sat), sfin));
-        // (no wait here: the linkage stages below end with the one wait that also covers these copies)
-    }
-    if (b->lev_sparse) {
-        // mm profiling on: the level mask, the windows' first level indices, one coverage byte (or two) per present level, the lists
-        if (redo) HIP_TRY(isx_wait_stream(ps));
-        int rc = ISX_OK;
-        const size_t n_lev = (size_t)b->sizes.n_entries, cov_bytes = n_lev * (size_t)b->lev_cov_bytes;
-        const size_t clon_bytes = (size_t)b->n_clon * sizeof(isx_rare), rare_bytes = p->prm.rarefied_coverage > 0 ? (size_t)b->n_rare * sizeof(isx_rare) : 0;
-        // a small batch's tables (a C2 batch: 5 + 12 MB) leave by copy kernel, not by DMA: see isx_copy_to_host_route
-        static const size_t lev_kernel_max = [] { const char *e = getenv("ISX_LEV_KERNEL_MAX"); return e ? (size_t)atoll(e) : (size_t)32 << 20; }();
-        const bool lev_by_kernel = s.out_pinned && (size_t)b->n_pos * b->lev_mask_bytes + cov_bytes + clon_bytes + rare_bytes <= lev_kernel_max;
-        std::vector<isx_copy_job> jobs;                             // (lev_by_kernel: all of the batch's tables in one launch)
-        auto fetch_lev = [&](void *hdst, const void *dsrc, size_t bytes) -> int {
-            if (!lev_by_kernel || ((reinterpret_cast<uintptr_t>(hdst) | reinterpret_cast<uintptr_t>(dsrc)) & 15)) return fetch(hdst, dsrc, bytes);
-            jobs.push_back(isx_copy_job{hdst, dsrc, bytes});
-            return ISX_OK;
-        };
-        if ((rc = fetch_lev(s.h_out + s.o_lmask, b->d_lev_mask, (size_t)b->n_pos * b->lev_mask_bytes)) != ISX_OK) return rc;
-        if ((rc = fetch_lev(s.h_out + s.o_lwin, b->d_lev_win_off, (size_t)b->n_win * sizeof(uint32_t))) != ISX_OK) return rc;
-        // what outgrows its pinned room (a deep sample's clonTR list, a coverage stream of more than four levels a position): plain vectors
-        auto fetch_or_big = [&](size_t off, size_t room, auto &big, const void *dsrc, size_t bytes) -> int {
-            big.clear();
-            if (bytes <= room) return fetch_lev(s.h_out + off, dsrc, bytes);
-            big.resize((bytes + sizeof(big[0]) - 1) / sizeof(big[0]));
-            if (p->bounce[0]) return bounce_d2h(p, big.data(), dsrc, bytes, sfin);
-            HIP_TRY(hipMemcpy(big.data(), dsrc, bytes, hipMemcpyDeviceToHost));
-            return ISX_OK;
-        };
-        if ((rc = fetch_or_big(s.o_lcov, s.lcov_room, s.lcov_big, b->d_lev_cov, cov_bytes)) != ISX_OK) return rc;
-        if ((rc = fetch_or_big(s.o_lclon, s.lclon_room, s.lclon_big, b->d_clon_list, clon_bytes)) != ISX_OK) return rc;
-        if (rare_bytes && (rc = fetch_or_big(s.o_lrare, s.lrare_room, s.lrare_big, b->d_rare, rare_bytes)) != ISX_OK) return rc;
-        if (!jobs.empty()) HIP_TRY(isx_copy_multi_to_host(jobs.data(), (int)jobs.size(), sfin));
-        s.sat_rows.resize((size_t)b->n_sat);
-        if (!s.sat_rows.empty()) HIP_TRY(isx_read_back(s.sat_rows.data(), b->d_sat, s.sat_rows.size() * sizeof(isx_sat), sfin));
-        // (no wait here: the linkage stages below end with the one wait that also covers these copies)
-        s.d2h_bytes += (int64_t)((size_t)b->n_pos * b->lev_mask_bytes + (size_t)b->n_win * 4 + cov_bytes + clon_bytes + rare_bytes + s.sat_rows.size() * sizeof(isx_sat));
-    }
-    // the linkage stages, on this finisher's queue behind the copies above; the bucket chain's one read-back is the wait for all of it
-    {
-        const int lrc = finish_pass_link(b, sfin);
-        if (lrc != ISX_OK) return lrc;
-        if (!(p->prm.enable_linkage && b->link_chain == 3)) HIP_TRY(isx_read_sync(sfin));
-    }
-    t_fin = now_ms();
-    if (dense && p->prm.rarefied_coverage > 0) {        // the sparse clonTR table, ascending positions
-        const size_t n_rare = b->n_rare;
-        isx_rare *rr = reinterpret_cast<isx_rare *>(s.h_small + s.o_rare);
-        s.rare_big.clear();
-        s.rare_dense = false;
-        if (n_rare > p->cap_rare || n_rare * 8 > (size_t)b->n_pos) {
-            // a deep sample: most positions reach the rarefied coverage, so the 8-byte list is no smaller than
-            // the 4-byte dense array (and would need sorting) -- or the device list overflowed: hand back the array
-            // (without want_counts there is no pinned room for it: deep samples are the exception, pinning 4 more bytes per
-            // position for every pipe is not worth it)
-            if (!p->pp.want_counts) {
-                if (s.clonr_big.size() < (size_t)b->n_pos) s.clonr_big.resize((size_t)b->n_pos);
-                if (p->bounce[0]) { const int rc = bounce_d2h(p, s.clonr_big.data(), b->d_clon_r, (size_t)b->n_pos * 4, sfin); if (rc != ISX_OK) return rc; }
-                else HIP_TRY(hipMemcpy(s.clonr_big.data(), b->d_clon_r, (size_t)b->n_pos * 4, hipMemcpyDeviceToHost));
-            } else if (redo && s.out_pinned)
-                HIP_TRY(hipMemcpy(s.h_out + s.o_clonr, b->d_clon_r, (size_t)b->n_pos * 4, hipMemcpyDeviceToHost));
-            s.rare_dense = true;
-        } else {
-            if (n_rare > p->rare_prefix || redo) {
-                if (n_rare > p->rare_prefix) { s.rare_big.resize(n_rare); rr = s.rare_big.data(); }
-                { const int prc = pull(rr, b->d_rare, n_rare * sizeof(isx_rare)); if (prc != ISX_OK) return prc; }
-            }
-            if (!b->ordered) std::sort(rr, rr + n_rare, [](const isx_rare &x, const isx_rare &y) { return x.gpos < y.gpos; });
-        }
-    }
-    t_rare = now_ms();
-    const size_t n_snv = (size_t)b->sizes.n_snv;
-    isx_snv *rows = reinterpret_cast<isx_snv *>(s.h_small + s.o_snv);
-    if (n_snv > p->snv_prefix || redo) {
-        if (n_snv > p->snv_prefix) { s.snv_big.resize(n_snv); rows = s.snv_big.data(); }
-        { const int prc = pull(rows, b->d_snv, n_snv * sizeof(isx_snv)); if (prc != ISX_OK) return prc; }
-    }
-    if (!b->ordered) std::sort(rows, rows + n_snv, [](const isx_snv &x, const isx_snv &y) { return x.gpos != y.gpos ? x.gpos < y.gpos : x.mm < y.mm; });
-    if (p->prm.enable_linkage) {
-        // the LD rows too: a blocking copy issued by the caller would queue behind the next batches' large transfers
-        s.ld_rows.resize((size_t)b->sizes.n_ld);
-        if (!s.ld_rows.empty() && b->ld_host && s.ld_rows.size() <= b->n_ld_host) memcpy(s.ld_rows.data(), b->ld_host, s.ld_rows.size() * sizeof(isx_ld));   // came home with the chain's state words
-        else if (!s.ld_rows.empty()) { const int rc = pull(s.ld_rows.data(), b->L.ld.p, s.ld_rows.size() * sizeof(isx_ld)); if (rc != ISX_OK) return rc; }
-    }
-    s.rows_checksum = bytes_checksum(s.ld_rows.data(), p->prm.enable_linkage ? s.ld_rows.size() * sizeof(isx_ld) : 0, bytes_checksum(rows, n_snv * sizeof(isx_snv), 0));
+    if (dense && (rc = fetch_dense_tables(f)) != ISX_OK) return rc;
+    if (b->lev_sparse && (rc = fetch_level_tables(f)) != ISX_OK) return rc;
+    if ((rc = link_and_wait(f)) != ISX_OK) return rc;
+    const double t_fin = now_ms();
+    if (dense && p->prm.rarefied_coverage > 0 && (rc = fetch_rare_table(f)) != ISX_OK) return rc;
+    const double t_rare = now_ms();
+    if ((rc = fetch_rows(f)) != ISX_OK) return rc;
+    r.d2h_bytes = slot_d2h_bytes(p, s);
     if (pipe_timing)
         fprintf(stderr, "[isx_pipe finisher] wait %.2f ms, finish (sizes, linkage) %.2f ms [device: sites %.2f allele %.2f group %.2f incr %.2f ld %.2f; %lld ao, %lld incr, %lld ld], clonTR list (%u) %.2f ms, snv rows (%zu) %.2f ms\n",
-                s.finish_wait_ms, t_fin - t_c0, b->tim.sites_ms, b->tim.allele_ms, b->tim.group_ms, b->tim.incr_ms, b->tim.ld_ms,
-                (long long)b->sizes.n_allele_obs, (long long)b->sizes.n_increments, (long long)b->sizes.n_ld, b->n_rare, t_rare - t_fin, n_snv, now_ms() - t_rare);
+                r.finish_wait_ms, t_fin - t_c0, b->tim.sites_ms, b->tim.allele_ms, b->tim.group_ms, b->tim.incr_ms, b->tim.ld_ms,
+                (long long)b->sizes.n_allele_obs, (long long)b->sizes.n_increments, (long long)b->sizes.n_ld, b->n_rare, t_rare - t_fin, (size_t)b->sizes.n_snv, now_ms() - t_rare);
     return ISX_OK;
 }
 
@@ -794,9 +1016,9 @@ static void finisher_main(isx_pipe *p, hipStream_t sfin)
         BamBatch *dead = nullptr;
         {
             std::lock_guard<std::mutex> lk(p->mu);
-            s.rc = rc; s.err.swap(err);
-            dead = s.dead_batch; s.dead_batch = nullptr;
-            s.state = 2;
+            s.tk.rc = rc; s.tk.err.swap(err);
+            dead = s.tk.dead_batch; s.tk.dead_batch = nullptr;
+            s.tk.state = 2;
         }
         p->cv_done.notify_all();
         // the front end's batch goes back to its handle outside the pipe's lock (retiring may free older batches: gigabytes);
@@ -828,7 +1050,7 @@ static void stager_main(isx_pipe *p)
             Slot &s = p->slots[(size_t)(job.ticket % (int64_t)p->slots.size())];
             std::string err(isx_last_error());
             std::lock_guard<std::mutex> lk(p->mu);
-            s.ticket = job.ticket; s.rc = rc; s.err.swap(err); s.state = 2;
+            s.tk.ticket = job.ticket; s.tk.rc = rc; s.tk.err.swap(err); s.tk.state = 2;
             p->next_ticket = job.ticket + 1;
         }
         p->cv_done.notify_all();
@@ -931,16 +1153,9 @@ int isx_pipe_create(isx_ctx *c, const isx_params *prm, const isx_pipe_params *pp
         return ISX_ERR_HIP;
     }
     p->slots.resize((size_t)pp->depth);
-    {   // ISX_PIPE_H2D_STREAMS=2 (tuning aid): the odd slots copy in through a queue of their own
-        const char *e2 = getenv("ISX_PIPE_H2D_STREAMS");
-        if (e2 && atoi(e2) >= 2 && pp->depth >= 2 && isx_side_stream_create(c, &p->s_h2d2) != hipSuccess) { p->s_h2d2 = nullptr; (void)hipGetLastError(); }
-    }
-    for (int i = 0; i < pp->depth && rc == ISX_OK; i++) {
-        rc = slot_batch_create(p, p->slots[(size_t)i], i);
-        if ((i & 1) && p->s_h2d2) p->slots[(size_t)i].h2d = p->s_h2d2;
-    }
+    for (int i = 0; i < pp->depth && rc == ISX_OK; i++) rc = slot_create(p, p->slots[(size_t)i], i);
     if (rc != ISX_OK) { pipe_free(p); return rc; }
-    if (!p->slots[0].out_pinned) {
+    if (!p->slots[0].res.out_pinned) {
         p->bounce_bytes = (size_t)16 << 20;
         for (int i = 0; i < 2 && rc == ISX_OK; i++) {
             if (isx_pin_malloc(reinterpret_cast<void **>(&p->bounce[i]), p->bounce_bytes) != hipSuccess ||
@@ -954,9 +1169,7 @@ int isx_pipe_create(isx_ctx *c, const isx_params *prm, const isx_pipe_params *pp
     {
         // a deep pipe whose copy-in no longer bounds the stream (reference-delta records halved it) is paced by how many batches
         // are being finished at a time -- sizes, linkage chain, small sorts: chains of short kernels and host syncs
-        int want = pp->depth >= 4 ? 4 : 2;
-        if (const char *e = getenv("ISX_PIPE_FINISHERS")) want = std::max(1, atoi(e));
-        want = std::min(want, pp->depth);
+        const int want = std::min(pp->depth >= 4 ? PIPE_FINISHERS_DEEP : 2, pp->depth);
         for (int i = 2; i < want; i++) {
             hipStream_t st = nullptr;
             if (isx_side_stream_create(c, &st) != hipSuccess) break;
@@ -973,7 +1186,7 @@ int isx_pipe_create(isx_ctx *c, const isx_params *prm, const isx_pipe_params *pp
 
 void isx_pipe_destroy(isx_pipe *p) { pipe_free(p); }
 
-// the pass queue and the copy-out queue of a slot whose copy-in has been enqueued (s.ev_h2d1 recorded), then the
+// the pass queue and the copy-out queue of a slot whose copy-in has been enqueued (s.in.ev_h2d1 recorded), then the
 // hand-over to the finisher
 static int enqueue_pass_impl(isx_pipe *p, Slot &s, int64_t n_pos, int64_t *ticket);
 
@@ -984,7 +1197,7 @@ static int enqueue_pass(isx_pipe *p, Slot &s, int64_t n_pos, int64_t *ticket)
     const int rc = enqueue_pass_impl(p, s, n_pos, ticket);
     if (rc != ISX_OK) {
         const std::string why(isx_last_error());
-        (void)isx_wait_stream(H2D(p, s));
+        (void)isx_wait_stream(p->s_h2d);
         (void)isx_wait_stream(p->ctx->pstream[s.b->ps]);
         (void)isx_wait_stream(p->s_d2h);
         isx_set_error(why);
@@ -1001,8 +1214,8 @@ static int enqueue_pass_impl(isx_pipe *p, Slot &s, int64_t n_pos, int64_t *ticke
     int rc = ISX_OK;
     // ---- pass queue ----
     std::unique_lock<std::mutex> launch_lk(p->launch_mu);
-    HIP_TRY(hipStreamWaitEvent(ps, s.ev_h2d1, 0));
-    if (dense && p->prm.rarefied_coverage > 0 && b->rare_dense)     // (a lean slot's shallow batch hands back the clonTR list alone)
+    HIP_TRY(hipStreamWaitEvent(ps, s.in.ev_h2d1, 0));
+    if (dense && p->prm.rarefied_coverage > 0 && b->form.rare_dense)        // (a lean slot's shallow batch hands back the clonTR list alone)
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->d_clon_r), 0x7FC00000, (size_t)n_pos, ps));
     if (linkage && p->rb == 4)
         launch_extract_gpos(nullptr, b->d_rec32, b->d_gbase, nullptr, b->d_gpos16, b->d_gbase, ISX_GROUP, b->n_rec, ps);
@@ -1014,43 +1227,32 @@ static int enqueue_pass_impl(isx_pipe *p, Slot &s, int64_t n_pos, int64_t *ticke
         b->publish_enqueued = true;
         if (c->unpublished[b->ps] == b) c->unpublished[b->ps] = nullptr;
     }
-    HIP_TRY(hipEventRecord(s.ev_pass, ps));
+    HIP_TRY(hipEventRecord(s.res.ev_pass, ps));
 
     // ---- copy-out queue ----
-    HIP_TRY(hipStreamWaitEvent(p->s_d2h, s.ev_pass, 0));
-    HIP_TRY(hipEventRecord(s.ev_d2h0, p->s_d2h));
+    HIP_TRY(hipStreamWaitEvent(p->s_d2h, s.res.ev_pass, 0));
+    HIP_TRY(hipEventRecord(s.res.ev_d2h0, p->s_d2h));
     const size_t snv_rows = std::min(p->snv_prefix, b->cap_snv);
     // the SNV rows (and clonTR entries) this pass will have produced: counted on the device, no fixed-size prefix
-    HIP_TRY(isx_copy_rows_to_host(s.h_small + s.o_snv, b->d_snv, b->d_cursors + CUR_SNV, b->base[CUR_SNV], (uint32_t)sizeof(isx_snv), snv_rows, p->s_d2h));
-    s.d2h_bytes = 0;                        // (finish_slot adds what really travelled)
-    if (dense) {
-        if (p->prm.rarefied_coverage > 0) {
-            const size_t n = std::min(p->rare_prefix, std::min(p->cap_rare, (size_t)n_pos));
-            HIP_TRY(isx_copy_rows_to_host(s.h_small + s.o_rare, b->d_rare, b->d_cursors + CUR_RARE, b->base[CUR_RARE], (uint32_t)sizeof(isx_rare), n, p->s_d2h));
-        }
-        if (!b->sparse_out) s.d2h_bytes += (int64_t)n_pos * 6;
+    HIP_TRY(isx_copy_rows_to_host(s.res.h_small + s.res.o_snv, b->d_snv, b->d_cursors + CUR_SNV, b->base[CUR_SNV], (uint32_t)sizeof(isx_snv), snv_rows, p->s_d2h));
+    if (dense && p->prm.rarefied_coverage > 0) {
+        const size_t n = std::min(p->rare_prefix, std::min(p->cap_rare, (size_t)n_pos));
+        HIP_TRY(isx_copy_rows_to_host(s.res.h_small + s.res.o_rare, b->d_rare, b->d_cursors + CUR_RARE, b->base[CUR_RARE], (uint32_t)sizeof(isx_rare), n, p->s_d2h));
     }
-    if (dense && s.out_pinned && !b->sparse_out) {     // (a plain result block / a shallow batch's tables are brought in by the finisher)
-        HIP_TRY(isx_copy_to_host(s.h_out + s.o_cov16, b->d_cov16, (size_t)n_pos * 2, p->s_d2h));
-        HIP_TRY(isx_copy_to_host(s.h_out + s.o_clon, b->d_clon, (size_t)n_pos * 4, p->s_d2h));
-        if (p->pp.want_counts) {
-            HIP_TRY(isx_copy_to_host(s.h_out + s.o_counts, b->d_counts, (size_t)n_pos * 16, p->s_d2h));
-            s.d2h_bytes += (int64_t)n_pos * 16;
-            if (p->prm.rarefied_coverage > 0) {
-                HIP_TRY(isx_copy_to_host(s.h_out + s.o_clonr, b->d_clon_r, (size_t)n_pos * 4, p->s_d2h));
-                s.d2h_bytes += (int64_t)n_pos * 4;
-            }
-        }
+    if (dense && s.res.out_pinned && !b->form.sparse_out) {     // (a plain result block / a shallow batch's tables are brought in by the finisher)
+        OutPiece o[4];
+        const int n = dense_out_pieces(p, s, LandedForm{}, o);
+        for (int i = 0; i < n; i++) HIP_TRY(isx_copy_to_host(s.res.h_out + o[i].off, o[i].src, o[i].bytes, p->s_d2h));
     }
-    HIP_TRY(hipEventRecord(s.ev_d2h1, p->s_d2h));
+    HIP_TRY(hipEventRecord(s.res.ev_d2h1, p->s_d2h));
     launch_lk.unlock();
     {
         std::lock_guard<std::mutex> lk(p->mu);
-        s.ticket = p->next_ticket++;
+        s.tk.ticket = p->next_ticket++;
         if (p->next_promise < p->next_ticket) p->next_promise = p->next_ticket;
-        s.state = 1; s.rc = ISX_OK;
-        *ticket = s.ticket;
-        p->work.push_back(s.ticket);
+        s.tk.state = 1; s.tk.rc = ISX_OK;
+        *ticket = s.tk.ticket;
+        p->work.push_back(s.tk.ticket);
     }
     p->cv_work.notify_one();
     return ISX_OK;
@@ -1078,7 +1280,7 @@ static int slot_acquire(isx_pipe *p, const char *who, Slot **out)
     Slot &s = p->slots[(size_t)(p->next_ticket % (int64_t)p->slots.size())];
     {
         std::lock_guard<std::mutex> lk(p->mu);
-        if (s.state != 0) { isx_set_error(std::string(who) + ": every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
+        if (s.tk.state != 0) { isx_set_error(std::string(who) + ": every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
     }
     HIP_TRY(hipSetDevice(p->ctx->device));
     *out = &s;
@@ -1097,7 +1299,7 @@ static int queue_for_stager(isx_pipe *p, isx_pipe::StageJob &&job, const char *w
         const int64_t t = p->next_promise, n = (int64_t)p->slots.size();
         const Slot &s = p->slots[(size_t)(t % n)];
         // the slot is free when the batch that had it last (ticket t - n) was staged, finished and released
-        if (t - n >= p->next_ticket || s.state != 0) { isx_set_error(std::string(who) + ": every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
+        if (t - n >= p->next_ticket || s.tk.state != 0) { isx_set_error(std::string(who) + ": every slot is in use (collect + release the oldest batch first)"); return ISX_ERR_STATE; }
         job.ticket = t;
         p->next_promise = t + 1;
         *ticket = t;
@@ -1118,22 +1320,22 @@ static int ring_feed_install(isx_pipe *p, Slot &s, RingFeed &r, int64_t &ring_gr
                              std::function<void(int, int64_t, int64_t)> &wave_flush)
 {
     if (p->ring_half <= 0) return ISX_OK;
-    HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
+    HIP_TRY(hipEventRecord(s.in.ev_h2d0, p->s_h2d));
     const size_t half_bytes = (size_t)p->ring_half * (size_t)p->rb, grp_bytes = (size_t)p->G * (size_t)p->rb;
-    uint8_t *d_rec = s.d_in + s.off_rec;
+    uint8_t *d_rec = s.in.d_in + s.in.off_rec;
     ring_groups = p->ring_half / (int64_t)p->G;
     wave_begin = [&s, &r](int h) {
-        if (s.ring_busy[h]) { const hipError_t e = isx_wait_event(s.ev_ring[h]); if (e != hipSuccess && r.err == hipSuccess) r.err = e; s.ring_busy[h] = false; }
+        if (s.in.ring_busy[h]) { const hipError_t e = isx_wait_event(s.in.ev_ring[h]); if (e != hipSuccess && r.err == hipSuccess) r.err = e; s.in.ring_busy[h] = false; }
     };
     wave_flush = [p, &s, &r, half_bytes, grp_bytes, d_rec](int h, int64_t g0, int64_t g1) {
         const size_t n = (size_t)(g1 - g0) * grp_bytes;
         // the observation encoder writes a layout that overflowed again from the start, inside one call: the count starts over at group 0
         // (the segment encoders' waves only ascend and submit resets the count before every attempt: for them this changes nothing)
         if (g0 == 0) r.bytes = 0;
-        hipError_t e = hipMemcpyAsync(d_rec + (size_t)g0 * grp_bytes, s.h_in + s.off_rec + (size_t)h * half_bytes, n, hipMemcpyHostToDevice, H2D(p, s));
-        if (e == hipSuccess) e = hipEventRecord(s.ev_ring[h], H2D(p, s));
+        hipError_t e = hipMemcpyAsync(d_rec + (size_t)g0 * grp_bytes, s.in.h_in + s.in.off_rec + (size_t)h * half_bytes, n, hipMemcpyHostToDevice, p->s_h2d);
+        if (e == hipSuccess) e = hipEventRecord(s.in.ev_ring[h], p->s_h2d);
         if (e != hipSuccess && r.err == hipSuccess) r.err = e;
-        s.ring_busy[h] = true;
+        s.in.ring_busy[h] = true;
         r.bytes += n;
     };
     return ISX_OK;
@@ -1146,40 +1348,24 @@ static int ring_feed_install(isx_pipe *p, Slot &s, RingFeed &r, int64_t &ring_gr
 static int slot_choose_windows(isx_pipe *p, Slot &s, uint32_t chunk, bool threads)
 {
     isx_batch *b = s.b;
-    DirThreads mt{*p->pool, s.dir_pmax, s.dir_smin};
-    const ChunkDir dir{s.cmin.data(), s.cmax.data(), s.cany.data(), b->n_rec / chunk, chunk};
-    b->W = choose_windows(b, b->n_pos, dir, threads ? &mt : nullptr, s.win, &b->packed);
-    b->n_win = (int)s.win.size();
-    if (s.win.size() > (size_t)p->pp.max_pos / 64 + 2) { isx_set_error("internal: window directory larger than the arena"); return ISX_ERR_STATE; }
-    memcpy(s.h_in + s.off_win, s.win.data(), s.win.size() * sizeof(uint2));
+    DirThreads mt{*p->pool, s.in.dir_pmax, s.in.dir_smin};
+    const ChunkDir dir{s.in.cmin.data(), s.in.cmax.data(), s.in.cany.data(), b->n_rec / chunk, chunk};
+    b->W = choose_windows(b, b->n_pos, dir, threads ? &mt : nullptr, s.in.win, &b->packed);
+    b->n_win = (int)s.in.win.size();
+    if (s.in.win.size() > (size_t)p->pp.max_pos / 64 + 2) { isx_set_error("internal: window directory larger than the arena"); return ISX_ERR_STATE; }
+    memcpy(s.in.h_in + s.in.off_win, s.in.win.data(), s.in.win.size() * sizeof(uint2));
     return ISX_OK;
 }
 
-// What a pass hands back depends on the batch's mean depth (n_obs / n_pos); a staged and a submitted batch must come to the same form
-// (the tests compare them byte for byte), so the cuts live here alone.
-constexpr double COV8_BELOW_DEPTH = 16.0;       // coverage travels in one byte a position
-constexpr double NIB_BELOW_DEPTH = 6.0;         // lean slots: ... in four bits (most windows stay within them)
-constexpr double LEV_COV8_BELOW_DEPTH = 64.0;   // level-sparse slots: a level's coverage in one byte (the few values >= 255 travel in a list)
-constexpr double RARE_DENSE_OBS_FACTOR = 4.0;   // lean slots: the clonTR table goes back dense once n_obs * 4 >= rarefied_coverage * n_pos
-
-// The output form of the pass over the batch in slot `s`, its launch geometry and entry slabs: b->n_pos / n_obs and the window choice
-// (b->W / packed / n_win: slot_choose_windows, or a wire's stored choice) are set.
+// The output form of the pass over the batch in slot `s` (form_for_depth), its launch geometry and entry slabs: b->n_pos / n_obs and the
+// window choice (b->W / packed / n_win: slot_choose_windows, or a wire's stored choice) are set.
 static int slot_shape_pass(isx_pipe *p, Slot &s)
 {
     isx_batch *b = s.b;
-    const bool dense = b->M == 1;
-    const double n_obs = (double)b->n_obs, n_pos = (double)b->n_pos;
-    // without a count table to hand back, the position-sized tables travel shrunk (see finish_slot): clonality as the list of
-    // values other than 1.0, coverage in one byte for a shallow batch
-    b->sparse_out = dense && b->d_clon_list != nullptr;
-    b->cov8_out = b->sparse_out && n_obs < COV8_BELOW_DEPTH * n_pos;
-    b->nib_out = b->cov8_out && b->lean && n_obs < NIB_BELOW_DEPTH * n_pos;
-    b->clon_dense = false;
-    b->rare_dense = !(b->lean && b->sparse_out) || n_obs * RARE_DENSE_OBS_FACTOR >= (double)p->prm.rarefied_coverage * n_pos;
-    if (b->lev_sparse) b->lev_cov_bytes = n_obs < LEV_COV8_BELOW_DEPTH * n_pos ? 1 : 2;
+    b->form = form_for_depth(b, p->prm.rarefied_coverage);
     const int rc = batch_set_geometry(b);
     if (rc != ISX_OK) return rc;
-    if (!dense && !b->lev_sparse) {
+    if (b->M > 1 && !b->lev_sparse) {
         const size_t used = (size_t)b->n_win * b->slab;
         if (used > b->slab_region) { isx_set_error("internal: entry slabs larger than the slot's region"); return ISX_ERR_STATE; }
         b->cap_ovf = b->cap_entries - used;
@@ -1193,24 +1379,24 @@ static void slot_bind_inputs(isx_pipe *p, Slot &s, uint8_t *resident_ref)
 {
     isx_batch *b = s.b;
     const bool linkage = p->prm.enable_linkage != 0;
-    uint8_t *rec = s.d_in + s.off_rec;
-    b->d_bounds = reinterpret_cast<int64_t *>(s.d_in + s.off_bounds);
-    b->d_win = reinterpret_cast<uint2 *>(s.d_in + s.off_win);
-    b->d_ref = resident_ref ? resident_ref : s.d_in + s.off_ref;
-    b->d_ref_n = s.ref_has_n ? b->d_ref + ref2_bytes(b->n_pos) : nullptr;
-    b->d_gbase = reinterpret_cast<uint32_t *>(s.d_in + s.off_gbase);
+    uint8_t *rec = s.in.d_in + s.in.off_rec;
+    b->d_bounds = reinterpret_cast<int64_t *>(s.in.d_in + s.in.off_bounds);
+    b->d_win = reinterpret_cast<uint2 *>(s.in.d_in + s.in.off_win);
+    b->d_ref = resident_ref ? resident_ref : s.in.d_in + s.in.off_ref;
+    b->d_ref_n = s.in.ref_has_n ? b->d_ref + ref2_bytes(b->n_pos) : nullptr;
+    b->d_gbase = reinterpret_cast<uint32_t *>(s.in.d_in + s.in.off_gbase);
     b->d_rec16 = p->rb == 2 ? reinterpret_cast<uint16_t *>(rec) : nullptr;
     b->d_rec32 = p->rb == 4 ? reinterpret_cast<uint32_t *>(rec) : nullptr;
     if (p->segs) {          // read-level: one pair id per record (reference-delta records carry the ids themselves), no run tables
         b->d_seg = p->drec ? nullptr : reinterpret_cast<uint4 *>(rec);
         b->d_drec = p->drec ? reinterpret_cast<uint4 *>(rec) : nullptr;
-        b->d_pair = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.d_in + s.off_pairs) : nullptr;
+        b->d_pair = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.in.d_in + s.in.off_pairs) : nullptr;
         b->d_pair_runs = nullptr; b->d_run_index = nullptr; b->n_runs = 0;
     } else {                // observation records: pair-id runs + their index (b->n_runs is the encoder's count)
         b->d_pair = nullptr;
-        b->d_pair_runs = linkage ? s.d_runs : nullptr;
-        b->d_run_index = linkage ? reinterpret_cast<uint32_t *>(s.d_in + s.off_ridx) : nullptr;
-        b->d_gpos16 = s.d_gpos16; b->gpos16_shift = 5;
+        b->d_pair_runs = linkage ? s.in.d_runs : nullptr;
+        b->d_run_index = linkage ? reinterpret_cast<uint32_t *>(s.in.d_in + s.in.off_ridx) : nullptr;
+        b->d_gpos16 = s.in.d_gpos16; b->gpos16_shift = 5;
     }
 }
 
@@ -1218,13 +1404,13 @@ static void slot_bind_inputs(isx_pipe *p, Slot &s, uint8_t *resident_ref)
 // lasts).  No entry when it cannot be made: the batch goes on with the planes that travelled, nothing leaks.
 static void ref_cache_insert(isx_pipe *p, Slot &s, const isx_ref_planes *rp, int64_t n_pos)
 {
-    const size_t rb_all = ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0);
+    const size_t rb_all = ref2_bytes(n_pos) + (s.in.ref_has_n ? refn_bytes(n_pos) : 0);
     if (p->ref_cache_bytes + rb_all > p->ref_cache_budget.load(std::memory_order_relaxed)) return;
     isx_pipe::RefEntry e;
     bool ok = isx_dev_malloc(reinterpret_cast<void **>(&e.d), rb_all + 64) == hipSuccess && hipEventCreateWithFlags(&e.ready, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMemcpyAsync(e.d, s.d_in + s.off_ref, rb_all, hipMemcpyDeviceToDevice, H2D(p, s)) == hipSuccess && hipEventRecord(e.ready, H2D(p, s)) == hipSuccess;
+    ok = ok && hipMemcpyAsync(e.d, s.in.d_in + s.in.off_ref, rb_all, hipMemcpyDeviceToDevice, p->s_h2d) == hipSuccess && hipEventRecord(e.ready, p->s_h2d) == hipSuccess;
     if (ok) {
-        e.bytes = rb_all; e.n_pos = n_pos; e.has_n = s.ref_has_n; e.sum = ref_plane_checksum(rp->plane2, n_pos);
+        e.bytes = rb_all; e.n_pos = n_pos; e.has_n = s.in.ref_has_n; e.sum = ref_plane_checksum(rp->plane2, n_pos);
         p->ref_cache_bytes += rb_all;
         p->ref_cache.emplace(rp->key, e);
     } else {
@@ -1243,13 +1429,13 @@ struct RefStage {
 
 // The reference planes of a bit-plane batch, BEFORE its records are made: the record pass compares the reads against a host-side copy
 // (J.ref2 / J.refn are set to it), and the planes leave at once so that the copy engine brings them in while the threads encode.
-// They travel in one of three ways; sets s.ref_has_n.  `rp`: the caller's planes, nullptr: packed from the codes `ref`.
+// They travel in one of three ways; sets s.in.ref_has_n.  `rp`: the caller's planes, nullptr: packed from the codes `ref`.
 static int stage_reference(isx_pipe *p, Slot &s, int64_t n_pos, const uint8_t *ref, const isx_ref_planes *rp, isxenc::SegJob &J, RefStage *out)
 {
     const bool ring = p->ring_half > 0;         // (the ring recorded ev_h2d0 when it was installed)
     const double t_r = now_ms();
     const size_t b2 = ((size_t)n_pos + 3) / 4, bn = ((size_t)n_pos + 7) / 8;
-    hipStream_t st = H2D(p, s);
+    hipStream_t st = p->s_h2d;
 
     // 1. resident under the caller's key: nothing is staged, nothing travels; the record pass compares against the caller's own planes
     const auto hit = rp && rp->key ? p->ref_cache.find(rp->key) : p->ref_cache.end();
@@ -1259,12 +1445,12 @@ static int stage_reference(isx_pipe *p, Slot &s, int64_t n_pos, const uint8_t *r
             isx_set_error("isx_pipe_submit_planes: the reference key stands for other planes (positions / non-ACGT plane / content differ)");
             return ISX_ERR_ARG;
         }
-        s.ref_has_n = e.has_n;
+        s.in.ref_has_n = e.has_n;
         J.ref2 = rp->plane2; J.refn = e.has_n ? rp->nplane : nullptr;
         out->resident = e.d;
         HIP_TRY(hipStreamWaitEvent(st, e.ready, 0));            // (the entry's own copy, enqueued by an earlier submit)
-        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, st));
-        HIP_TRY(hipEventRecord(s.ev_h2da, st));
+        if (!ring) HIP_TRY(hipEventRecord(s.in.ev_h2d0, st));
+        HIP_TRY(hipEventRecord(s.in.ev_h2da, st));
         out->early = true;
         out->host_ms = now_ms() - t_r;
         return ISX_OK;
@@ -1275,28 +1461,25 @@ static int stage_reference(isx_pipe *p, Slot &s, int64_t n_pos, const uint8_t *r
     const bool first_trip = rp && rp->key && p->ref_cache_budget.load(std::memory_order_relaxed) > 0;
     if (rp && !first_trip && isx_host_is_registered(rp->plane2, b2) && (!rp->nplane || isx_host_is_registered(rp->nplane, bn))) {
         const bool any_n = rp->nplane && plane_any(*p->pool, rp->nplane, bn);
-        s.ref_has_n = any_n;
+        s.in.ref_has_n = any_n;
         J.ref2 = rp->plane2; J.refn = any_n ? rp->nplane : nullptr;
         out->host_ms = now_ms() - t_r;
-        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, st));
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, rp->plane2, b2, hipMemcpyHostToDevice, st));
-        if (any_n) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref + ref2_bytes(n_pos), rp->nplane, bn, hipMemcpyHostToDevice, st));
-        if (!ring) HIP_TRY(hipEventRecord(s.ev_h2da, st));
+        if (!ring) HIP_TRY(hipEventRecord(s.in.ev_h2d0, st));
+        HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ref, rp->plane2, b2, hipMemcpyHostToDevice, st));
+        if (any_n) HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ref + ref2_bytes(n_pos), rp->nplane, bn, hipMemcpyHostToDevice, st));
+        if (!ring) HIP_TRY(hipEventRecord(s.in.ev_h2da, st));
         out->early = true;
         return ISX_OK;
     }
 
     // 3. through the slot's staging: the caller's planes copied, or the codes packed
-    uint8_t *h2 = s.h_in + s.off_ref, *hn = h2 + ref2_bytes(n_pos);
-    s.ref_has_n = rp ? copy_ref_planes(*p->pool, rp, n_pos, h2, hn) : isxenc::pack_ref_planes(*p->pool, ref, n_pos, h2, hn);
-    J.ref2 = h2; J.refn = s.ref_has_n ? hn : nullptr;
+    uint8_t *h2 = s.in.h_in + s.in.off_ref, *hn = h2 + ref2_bytes(n_pos);
+    s.in.ref_has_n = rp ? copy_ref_planes(*p->pool, rp, n_pos, h2, hn) : isxenc::pack_ref_planes(*p->pool, ref, n_pos, h2, hn);
+    J.ref2 = h2; J.refn = s.in.ref_has_n ? hn : nullptr;
     out->host_ms = now_ms() - t_r;
-    // (ISX_PIPE_LATE_DMA=1: every copy after the host pass, as before round 5 -- same-box A/B)
-    static const bool late_dma = getenv("ISX_PIPE_LATE_DMA") != nullptr;
-    if (late_dma) return ISX_OK;
-    if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, st));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, h2, ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0), hipMemcpyHostToDevice, st));
-    if (!ring) HIP_TRY(hipEventRecord(s.ev_h2da, st));
+    if (!ring) HIP_TRY(hipEventRecord(s.in.ev_h2d0, st));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ref, h2, ref2_bytes(n_pos) + (s.in.ref_has_n ? refn_bytes(n_pos) : 0), hipMemcpyHostToDevice, st));
+    if (!ring) HIP_TRY(hipEventRecord(s.in.ev_h2da, st));
     out->early = true;
     if (rp && rp->key) ref_cache_insert(p, s, rp, n_pos);
     return ISX_OK;
@@ -1319,31 +1502,31 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
     // ---- host threads: records + group bases (+ pair-id runs) into pinned staging, reference codes, bounds ----
     const double t0 = now_ms();
     const bool ring = p->ring_half > 0;
-    uint8_t *d_rec = s.d_in + s.off_rec;
+    uint8_t *d_rec = s.in.d_in + s.in.off_rec;
     RingFeed feed;
     J.n_obs = n_obs; J.n_pos = n_pos; J.record_bytes = p->rb;
-    J.rec = s.h_in + s.off_rec; J.gbase = reinterpret_cast<uint32_t *>(s.h_in + s.off_gbase);
+    J.rec = s.in.h_in + s.in.off_rec; J.gbase = reinterpret_cast<uint32_t *>(s.in.h_in + s.in.off_gbase);
     J.pair_out = nullptr;
-    J.cmin = s.cmin.data(); J.cmax = s.cmax.data(); J.cany = s.cany.data();
+    J.cmin = s.in.cmin.data(); J.cmax = s.in.cmax.data(); J.cany = s.in.cany.data();
     J.cap_rec = p->cap_rec;
     if ((rc = ring_feed_install(p, s, feed, J.ring_groups, J.wave_begin, J.wave_flush)) != ISX_OK) return rc;
     int erc = 0;
     for (int attempt = 0;; attempt++) {
         if (linkage) {
-            J.runs_out = s.h_runs; J.cap_runs = s.cap_runs;
-            J.run_index_out = reinterpret_cast<uint32_t *>(s.h_in + s.off_ridx);
+            J.runs_out = s.in.h_runs; J.cap_runs = s.in.cap_runs;
+            J.run_index_out = reinterpret_cast<uint32_t *>(s.in.h_in + s.in.off_ridx);
         }
         J.slack = p->slack;
         feed.bytes = 0;
         erc = isxenc::encode_obs(*p->pool, J);
-        if (erc != isxenc::ENC_OK || !linkage || J.n_runs <= s.cap_runs || attempt == 1) break;
+        if (erc != isxenc::ENC_OK || !linkage || J.n_runs <= s.in.cap_runs || attempt == 1) break;
         // more pair-id runs than any batch of this slot had (short fragments): larger blocks, encode again
-        HIP_TRY(isx_wait_stream(H2D(p, s)));
-        host_block_free(s.h_runs, s.runs_pinned); s.h_runs = nullptr;
-        isx_dev_free(s.d_runs); s.d_runs = nullptr;
-        s.cap_runs = J.n_runs + J.n_runs / 4 + 4096;
-        { const int hrc = host_block_alloc(reinterpret_cast<void **>(&s.h_runs), s.cap_runs * sizeof(isxenc::PairRun), s.runs_pinned); if (hrc != ISX_OK) return hrc; }
-        HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.d_runs), s.cap_runs * sizeof(uint2)));
+        HIP_TRY(isx_wait_stream(p->s_h2d));
+        host_block_free(s.in.h_runs, s.in.runs_pinned); s.in.h_runs = nullptr;
+        isx_dev_free(s.in.d_runs); s.in.d_runs = nullptr;
+        s.in.cap_runs = J.n_runs + J.n_runs / 4 + 4096;
+        { const int hrc = host_block_alloc(reinterpret_cast<void **>(&s.in.h_runs), s.in.cap_runs * sizeof(isxenc::PairRun), s.in.runs_pinned); if (hrc != ISX_OK) return hrc; }
+        HIP_TRY(isx_dev_malloc(reinterpret_cast<void **>(&s.in.d_runs), s.in.cap_runs * sizeof(uint2)));
     }
     const double t_enc = now_ms();
     if (feed.err != hipSuccess) { isx_set_error(std::string("isx_pipe_submit: staging ring: ") + hipGetErrorString(feed.err)); return ISX_ERR_HIP; }
@@ -1351,13 +1534,13 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
     if (erc == isxenc::ENC_MM_RANGE) { isx_set_error("an observation has mm >= 256"); return ISX_ERR_MM_RANGE; }
     if (erc == isxenc::ENC_BAD_POS) { isx_set_error("observation gpos >= n_pos"); return ISX_ERR_ARG; }
     if (linkage) {          // pair-id runs + run index were written into pinned staging by the encoder's threads
-        if (J.n_runs > s.cap_runs) { isx_set_error("isx_pipe_submit: internal: pair-id run table did not fit after growing it"); return ISX_ERR_STATE; }
+        if (J.n_runs > s.in.cap_runs) { isx_set_error("isx_pipe_submit: internal: pair-id run table did not fit after growing it"); return ISX_ERR_STATE; }
         b->n_runs = (uint32_t)J.n_runs;
     }
     if (J.passes > 1 && J.n_groups_in > 0)            // remember how jumpy this stream is: the next batch gets its slack up front
         p->slack = std::max(p->slack, 1.25 * ((double)J.n_groups_real / (double)J.n_groups_in - 1.0) + 0.01);
-    s.ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, s.h_in + s.off_ref, s.h_in + s.off_ref + ref2_bytes(n_pos));
-    memcpy(s.h_in + s.off_bounds, split_bounds, (size_t)(n_splits + 1) * sizeof(int64_t));
+    s.in.ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, s.in.h_in + s.in.off_ref, s.in.h_in + s.in.off_ref + ref2_bytes(n_pos));
+    memcpy(s.in.h_in + s.in.off_bounds, split_bounds, (size_t)(n_splits + 1) * sizeof(int64_t));
 
     // ---- this batch's geometry ----
     b->n_pos = n_pos; b->n_obs = n_obs; b->n_splits = n_splits; b->n_rec = (uint64_t)J.n_rec;
@@ -1365,43 +1548,43 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
     if ((rc = slot_choose_windows(p, s, ISX_CHUNK, false)) != ISX_OK) return rc;
     if ((rc = slot_shape_pass(p, s)) != ISX_OK) return rc;
     slot_bind_inputs(p, s, nullptr);
-    s.encode_ms = (float)(now_ms() - t0);
-    s.encode_passes = J.passes;
+    s.in.encode_ms = (float)(now_ms() - t0);
+    s.in.encode_passes = J.passes;
     if (pipe_timing)
         fprintf(stderr, "[isx_pipe_submit] records %.2f ms (%d pass), reference + bounds + windows %.2f ms; %lld obs, %lld runs\n",
                 t_enc - t0, J.passes, now_ms() - t_enc, (long long)n_obs, (long long)J.n_runs);
 
     // ---- copy-in queue ----
-    if (!ring) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-    const size_t ref_bytes = ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0);   // 2-bit plane (+ the non-ACGT bit plane)
-    const size_t head = (size_t)(n_splits + 1) * sizeof(int64_t) + s.win.size() * sizeof(uint2) + ref_bytes;
+    if (!ring) HIP_TRY(hipEventRecord(s.in.ev_h2d0, p->s_h2d));
+    const size_t ref_bytes = ref2_bytes(n_pos) + (s.in.ref_has_n ? refn_bytes(n_pos) : 0);   // 2-bit plane (+ the non-ACGT bit plane)
+    const size_t head = (size_t)(n_splits + 1) * sizeof(int64_t) + s.in.win.size() * sizeof(uint2) + ref_bytes;
     // the stream is followed by a tail of padding records / zero bases (see ISX_TAIL_BYTES): the slot's arena still
     // holds the previous batch there
-    memset(s.h_in + s.off_gbase + (size_t)(b->n_rec / p->G) * sizeof(uint32_t), 0, ISX_TAIL_GROUPS * sizeof(uint32_t));
+    memset(s.in.h_in + s.in.off_gbase + (size_t)(b->n_rec / p->G) * sizeof(uint32_t), 0, ISX_TAIL_GROUPS * sizeof(uint32_t));
     const size_t gb_bytes = ((size_t)(b->n_rec / p->G) + ISX_TAIL_GROUPS) * sizeof(uint32_t), rec_bytes = (size_t)b->n_rec * p->rb + ISX_TAIL_BYTES;
     // bounds | windows | reference planes: what is used of each region, not the regions (a slot is sized for the largest batch)
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_bounds, s.h_in + s.off_bounds, (size_t)(n_splits + 1) * sizeof(int64_t), hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_win, s.h_in + s.off_win, s.win.size() * sizeof(uint2), hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, s.h_in + s.off_ref, ref_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_gbase, s.h_in + s.off_gbase, gb_bytes, hipMemcpyHostToDevice, H2D(p, s)));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_bounds, s.in.h_in + s.in.off_bounds, (size_t)(n_splits + 1) * sizeof(int64_t), hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_win, s.in.h_in + s.in.off_win, s.in.win.size() * sizeof(uint2), hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ref, s.in.h_in + s.in.off_ref, ref_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_gbase, s.in.h_in + s.in.off_gbase, gb_bytes, hipMemcpyHostToDevice, p->s_h2d));
     if (ring) {             // the records left wave by wave; the tail is written on the device
-        if (p->rb == 2) HIP_TRY(hipMemsetD8Async(reinterpret_cast<hipDeviceptr_t>(d_rec + (size_t)b->n_rec * 2), 0xFF, ISX_TAIL_BYTES, H2D(p, s)));
-        else HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rec + (size_t)b->n_rec * 4), (int)ISX_PAD32, ISX_TAIL_BYTES / 4, H2D(p, s)));
+        if (p->rb == 2) HIP_TRY(hipMemsetD8Async(reinterpret_cast<hipDeviceptr_t>(d_rec + (size_t)b->n_rec * 2), 0xFF, ISX_TAIL_BYTES, p->s_h2d));
+        else HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rec + (size_t)b->n_rec * 4), (int)ISX_PAD32, ISX_TAIL_BYTES / 4, p->s_h2d));
         if (feed.bytes != (size_t)b->n_rec * p->rb) { isx_set_error("internal: the staging ring did not carry the whole stream"); return ISX_ERR_STATE; }
     } else {
-        if (p->rb == 2) memset(s.h_in + s.off_rec + (size_t)b->n_rec * 2, 0xFF, ISX_TAIL_BYTES);
-        else std::fill_n(reinterpret_cast<uint32_t *>(s.h_in + s.off_rec + (size_t)b->n_rec * 4), ISX_TAIL_BYTES / 4, (uint32_t)ISX_PAD32);
-        HIP_TRY(hipMemcpyAsync(d_rec, s.h_in + s.off_rec, rec_bytes, hipMemcpyHostToDevice, H2D(p, s)));
+        if (p->rb == 2) memset(s.in.h_in + s.in.off_rec + (size_t)b->n_rec * 2, 0xFF, ISX_TAIL_BYTES);
+        else std::fill_n(reinterpret_cast<uint32_t *>(s.in.h_in + s.in.off_rec + (size_t)b->n_rec * 4), ISX_TAIL_BYTES / 4, (uint32_t)ISX_PAD32);
+        HIP_TRY(hipMemcpyAsync(d_rec, s.in.h_in + s.in.off_rec, rec_bytes, hipMemcpyHostToDevice, p->s_h2d));
     }
-    s.h2d_bytes = (int64_t)(head + gb_bytes + rec_bytes);
+    s.in.h2d_bytes = (int64_t)(head + gb_bytes + rec_bytes);
     if (linkage) {
         const size_t rb = (size_t)b->n_runs * sizeof(isxenc::PairRun), ib = (size_t)(b->n_rec / ISX_CHUNK) * sizeof(uint32_t);
-        HIP_TRY(hipMemcpyAsync(s.d_runs, s.h_runs, rb, hipMemcpyHostToDevice, H2D(p, s)));
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ridx, s.h_in + s.off_ridx, ib, hipMemcpyHostToDevice, H2D(p, s)));
-        s.h2d_bytes += (int64_t)(rb + ib);
+        HIP_TRY(hipMemcpyAsync(s.in.d_runs, s.in.h_runs, rb, hipMemcpyHostToDevice, p->s_h2d));
+        HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ridx, s.in.h_in + s.in.off_ridx, ib, hipMemcpyHostToDevice, p->s_h2d));
+        s.in.h2d_bytes += (int64_t)(rb + ib);
     }
-    HIP_TRY(hipEventRecord(s.ev_h2d1, H2D(p, s)));
-    s.h2d_split = false;
+    HIP_TRY(hipEventRecord(s.in.ev_h2d1, p->s_h2d));
+    s.in.h2d_split = false;
 
     return enqueue_pass(p, s, n_pos, ticket);
 }
@@ -1412,7 +1595,7 @@ static int submit_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, int32_t
 // again).  Returns the encoder's status (isxenc::SEG_*).
 static int encode_reads(isx_pipe *p, Slot &s, isxenc::SegJob &J, bool planes_in, RingFeed &feed)
 {
-    s.encode_passes = 1;
+    s.in.encode_passes = 1;
     if (!p->drec) return isxenc::encode_segs(*p->pool, J);
     std::vector<int64_t> exact;
     for (int attempt = 0;; attempt++) {
@@ -1429,7 +1612,7 @@ static int encode_reads(isx_pipe *p, Slot &s, isxenc::SegJob &J, bool planes_in,
         for (int64_t v : exact) tot += v;
         const int64_t n_t = (int64_t)exact.size(), base_tot = J.n_rec / ISX_DREC_GROUP - n_t * p->dslack;
         p->dslack = std::max<int64_t>(p->dslack, 1 + (tot - base_tot + n_t - 1) / std::max<int64_t>(n_t, 1));
-        s.encode_passes = 2;
+        s.in.encode_passes = 2;
     }
 }
 
@@ -1452,10 +1635,10 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
     // ---- host threads: records + group bases (+ pair ids) into pinned staging, reference codes, bounds ----
     const double t0 = now_ms();
     J.n_pos = n_pos; J.n_mm_bins = b->M;
-    J.rec = reinterpret_cast<uint32_t *>(s.h_in + s.off_rec);
-    J.gbase = reinterpret_cast<uint32_t *>(s.h_in + s.off_gbase);
-    J.pair_out = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.h_in + s.off_pairs) : nullptr;
-    J.cmin = s.cmin.data(); J.cmax = s.cmax.data(); J.cany = s.cany.data();
+    J.rec = reinterpret_cast<uint32_t *>(s.in.h_in + s.in.off_rec);
+    J.gbase = reinterpret_cast<uint32_t *>(s.in.h_in + s.in.off_gbase);
+    J.pair_out = linkage && !p->drec ? reinterpret_cast<uint32_t *>(s.in.h_in + s.in.off_pairs) : nullptr;
+    J.cmin = s.in.cmin.data(); J.cmax = s.in.cmax.data(); J.cany = s.in.cany.data();
     J.cap_rec = p->cap_rec;
     const bool ring = p->ring_half > 0;
     RingFeed feed;
@@ -1476,20 +1659,20 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
     if (rs.early && !ring) {
         // the records leave as soon as they exist; the window directory below is made while they travel
         const size_t gb_bytes0 = (size_t)(J.n_rec / (int64_t)p->G) * sizeof(uint32_t), rec_bytes0 = (size_t)J.n_rec * (size_t)p->rb;
-        HIP_TRY(hipEventRecord(s.ev_h2db, H2D(p, s)));
-        if (s.off_pairs == s.off_rec && s.off_ridx == s.off_rec && s.off_rec - s.off_gbase < ((size_t)2 << 20)) {
+        HIP_TRY(hipEventRecord(s.in.ev_h2db, p->s_h2d));
+        if (s.in.off_pairs == s.in.off_rec && s.in.off_ridx == s.in.off_rec && s.in.off_rec - s.in.off_gbase < ((size_t)2 << 20)) {
             // group bases | records lie side by side in both arenas (nothing between them in a pipe of reference-delta records): ONE copy --
             // a small copy of its own is a blit kernel and a queue entry; the unused tail of the group bases' region (< 2 MB) travels along
-            HIP_TRY(hipMemcpyAsync(s.d_in + s.off_gbase, s.h_in + s.off_gbase, (s.off_rec - s.off_gbase) + rec_bytes0, hipMemcpyHostToDevice, H2D(p, s)));
+            HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_gbase, s.in.h_in + s.in.off_gbase, (s.in.off_rec - s.in.off_gbase) + rec_bytes0, hipMemcpyHostToDevice, p->s_h2d));
         } else {
-            HIP_TRY(hipMemcpyAsync(s.d_in + s.off_gbase, s.h_in + s.off_gbase, gb_bytes0, hipMemcpyHostToDevice, H2D(p, s)));
-            HIP_TRY(hipMemcpyAsync(s.d_in + s.off_rec, s.h_in + s.off_rec, rec_bytes0, hipMemcpyHostToDevice, H2D(p, s)));
+            HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_gbase, s.in.h_in + s.in.off_gbase, gb_bytes0, hipMemcpyHostToDevice, p->s_h2d));
+            HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_rec, s.in.h_in + s.in.off_rec, rec_bytes0, hipMemcpyHostToDevice, p->s_h2d));
         }
         early_rec = true;
     }
-    if (!planes_in) s.ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, s.h_in + s.off_ref, s.h_in + s.off_ref + ref2_bytes(n_pos));
+    if (!planes_in) s.in.ref_has_n = isxenc::pack_ref_planes(*p->pool, ref, n_pos, s.in.h_in + s.in.off_ref, s.in.h_in + s.in.off_ref + ref2_bytes(n_pos));
     const double t_ref = now_ms();
-    memcpy(s.h_in + s.off_bounds, split_bounds, (size_t)(n_splits + 1) * sizeof(int64_t));
+    memcpy(s.in.h_in + s.in.off_bounds, split_bounds, (size_t)(n_splits + 1) * sizeof(int64_t));
 
     // ---- this batch's geometry ----
     b->n_pos = n_pos; b->n_obs = J.n_bases; b->n_splits = n_splits; b->n_rec = (uint64_t)J.n_rec;
@@ -1497,35 +1680,35 @@ static int submit_segs_common(isx_pipe *p, int64_t n_pos, const uint8_t *ref, in
     if ((rc = slot_choose_windows(p, s, p->G, true)) != ISX_OK) return rc;
     if ((rc = slot_shape_pass(p, s)) != ISX_OK) return rc;
     slot_bind_inputs(p, s, rs.resident);
-    s.encode_ms = (float)(now_ms() - t0);
+    s.in.encode_ms = (float)(now_ms() - t0);
     if (pipe_timing)
         fprintf(stderr, "[isx_pipe_submit_reads] records %.2f ms, reference %.2f ms, bounds + windows %.2f ms; %lld segments, %lld records%s\n",
                 t_enc - t0 - rs.host_ms, t_ref - t_enc + rs.host_ms, now_ms() - t_ref, (long long)J.n_seg, (long long)J.n_rec, planes_in ? " (bit planes)" : "");
     const double t_q0 = now_ms();
 
     // ---- copy-in queue: bounds | windows | reference codes, then group bases (| pair ids) | records ----
-    if (!ring && !rs.early) HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-    const size_t ref_bytes = ref2_bytes(n_pos) + (s.ref_has_n ? refn_bytes(n_pos) : 0);   // 2-bit plane (+ the non-ACGT bit plane)
-    const size_t head = (size_t)(n_splits + 1) * sizeof(int64_t) + s.win.size() * sizeof(uint2) + ref_bytes;
+    if (!ring && !rs.early) HIP_TRY(hipEventRecord(s.in.ev_h2d0, p->s_h2d));
+    const size_t ref_bytes = ref2_bytes(n_pos) + (s.in.ref_has_n ? refn_bytes(n_pos) : 0);   // 2-bit plane (+ the non-ACGT bit plane)
+    const size_t head = (size_t)(n_splits + 1) * sizeof(int64_t) + s.in.win.size() * sizeof(uint2) + ref_bytes;
     const size_t gb_bytes = (size_t)(b->n_rec / p->G) * sizeof(uint32_t), rec_bytes = (size_t)b->n_rec * (size_t)p->rb;
     // bounds | windows | reference planes: what is used of each region, not the regions (a slot is sized for the largest batch)
-    if (s.off_win - s.off_bounds < ((size_t)1 << 20)) {          // bounds | windows in one copy (the bounds' region is a slot's max_splits: small)
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_bounds, s.h_in + s.off_bounds, (s.off_win - s.off_bounds) + s.win.size() * sizeof(uint2), hipMemcpyHostToDevice, H2D(p, s)));
+    if (s.in.off_win - s.in.off_bounds < ((size_t)1 << 20)) {          // bounds | windows in one copy (the bounds' region is a slot's max_splits: small)
+        HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_bounds, s.in.h_in + s.in.off_bounds, (s.in.off_win - s.in.off_bounds) + s.in.win.size() * sizeof(uint2), hipMemcpyHostToDevice, p->s_h2d));
     } else {
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_bounds, s.h_in + s.off_bounds, (size_t)(n_splits + 1) * sizeof(int64_t), hipMemcpyHostToDevice, H2D(p, s)));
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_win, s.h_in + s.off_win, s.win.size() * sizeof(uint2), hipMemcpyHostToDevice, H2D(p, s)));
+        HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_bounds, s.in.h_in + s.in.off_bounds, (size_t)(n_splits + 1) * sizeof(int64_t), hipMemcpyHostToDevice, p->s_h2d));
+        HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_win, s.in.h_in + s.in.off_win, s.in.win.size() * sizeof(uint2), hipMemcpyHostToDevice, p->s_h2d));
     }
-    if (!rs.early) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, s.h_in + s.off_ref, ref_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    if (!early_rec) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_gbase, s.h_in + s.off_gbase, gb_bytes, hipMemcpyHostToDevice, H2D(p, s)));
+    if (!rs.early) HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ref, s.in.h_in + s.in.off_ref, ref_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    if (!early_rec) HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_gbase, s.in.h_in + s.in.off_gbase, gb_bytes, hipMemcpyHostToDevice, p->s_h2d));
     if (ring) { if (feed.bytes != rec_bytes) { isx_set_error("internal: the staging ring did not carry the whole stream"); return ISX_ERR_STATE; } }
-    else if (!early_rec) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_rec, s.h_in + s.off_rec, rec_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    s.h2d_bytes = (int64_t)(head + gb_bytes + rec_bytes) - (rs.resident ? (int64_t)ref_bytes : 0);
+    else if (!early_rec) HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_rec, s.in.h_in + s.in.off_rec, rec_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    s.in.h2d_bytes = (int64_t)(head + gb_bytes + rec_bytes) - (rs.resident ? (int64_t)ref_bytes : 0);
     if (linkage && !p->drec) {
-        HIP_TRY(hipMemcpyAsync(s.d_in + s.off_pairs, s.h_in + s.off_pairs, (size_t)b->n_rec * sizeof(uint32_t), hipMemcpyHostToDevice, H2D(p, s)));
-        s.h2d_bytes += (int64_t)b->n_rec * 4;
+        HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_pairs, s.in.h_in + s.in.off_pairs, (size_t)b->n_rec * sizeof(uint32_t), hipMemcpyHostToDevice, p->s_h2d));
+        s.in.h2d_bytes += (int64_t)b->n_rec * 4;
     }
-    HIP_TRY(hipEventRecord(s.ev_h2d1, H2D(p, s)));
-    s.h2d_split = early_rec;
+    HIP_TRY(hipEventRecord(s.in.ev_h2d1, p->s_h2d));
+    s.in.h2d_split = early_rec;
     const double t_q1 = now_ms();
     rc = enqueue_pass(p, s, n_pos, ticket);
     if (pipe_timing) fprintf(stderr, "[isx_pipe_submit_reads] copy-in queue %.2f ms, pass + copy-out queue %.2f ms\n", t_q1 - t_q0, now_ms() - t_q1);
@@ -1706,23 +1889,23 @@ int isx_pipe_submit_wire(isx_pipe *p, const isx_wire *w, int64_t *ticket)
     const double t0 = now_ms();
     b->n_pos = w->n_pos; b->n_obs = w->n_bases; b->n_splits = w->n_splits; b->n_rec = (uint64_t)w->n_rec;
     b->n_pairs = w->n_pairs;
-    s.ref_has_n = w->ref_has_n;
+    s.in.ref_has_n = w->ref_has_n;
     b->packed = w->packed; b->W = w->W;             // the choice stage_common made, replayed
     b->n_win = (int)(w->win_bytes / sizeof(uint2));
     if ((rc = slot_shape_pass(p, s)) != ISX_OK) return rc;
     slot_bind_inputs(p, s, w->d_ref);               // (a kept reference: the wire's own device copy, nothing to bring in)
-    HIP_TRY(hipEventRecord(s.ev_h2d0, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_bounds, w->h + w->o_bounds, w->bounds_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_win, w->h + w->o_win, w->win_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    if (!w->d_ref) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_ref, w->h + w->o_ref, w->ref_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_gbase, w->h + w->o_gbase, w->gbase_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    if (w->pairs_bytes) HIP_TRY(hipMemcpyAsync(s.d_in + s.off_pairs, w->h + w->o_pairs, w->pairs_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipMemcpyAsync(s.d_in + s.off_rec, w->h + w->o_rec, w->rec_bytes, hipMemcpyHostToDevice, H2D(p, s)));
-    HIP_TRY(hipEventRecord(s.ev_h2d1, H2D(p, s)));
-    s.h2d_split = false;
-    s.h2d_bytes = isx_wire_bytes(w);
-    s.encode_ms = (float)(now_ms() - t0);       // (what this submit itself spent on the host: enqueueing)
-    s.encode_passes = 0;                        // staged ahead of time
+    HIP_TRY(hipEventRecord(s.in.ev_h2d0, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_bounds, w->h + w->o_bounds, w->bounds_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_win, w->h + w->o_win, w->win_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    if (!w->d_ref) HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_ref, w->h + w->o_ref, w->ref_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_gbase, w->h + w->o_gbase, w->gbase_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    if (w->pairs_bytes) HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_pairs, w->h + w->o_pairs, w->pairs_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipMemcpyAsync(s.in.d_in + s.in.off_rec, w->h + w->o_rec, w->rec_bytes, hipMemcpyHostToDevice, p->s_h2d));
+    HIP_TRY(hipEventRecord(s.in.ev_h2d1, p->s_h2d));
+    s.in.h2d_split = false;
+    s.in.h2d_bytes = isx_wire_bytes(w);
+    s.in.encode_ms = (float)(now_ms() - t0);       // (what this submit itself spent on the host: enqueueing)
+    s.in.encode_passes = 0;                        // staged ahead of time
     return enqueue_pass(p, s, w->n_pos, ticket);
 }
 
@@ -1840,7 +2023,7 @@ int isx_pipe_submit_bam(isx_pipe *p, isx_bam *bam, const struct isx_bam_params_s
     if (rc == ISX_OK) {
         std::lock_guard<std::mutex> lk(p->mu);
         Slot &s = p->slots[(size_t)(*ticket % (int64_t)p->slots.size())];
-        if (s.ticket == *ticket && s.state == 1) s.dead_batch = Q.release();
+        if (s.tk.ticket == *ticket && s.tk.state == 1) s.tk.dead_batch = Q.release();
     }
     if (Q) bam_batch_retire(Q.release());
     if (pipe_timing)
@@ -1860,62 +2043,62 @@ int isx_pipe_collect(isx_pipe *p, int64_t ticket, isx_pipe_result *out)
         const double t0 = now_ms();
         std::unique_lock<std::mutex> lk(p->mu);
         if (ticket < p->next_promise) p->cv_done.wait(lk, [&] { return p->next_ticket > ticket; });     // queued for the stager: staged first
-        if (s.ticket != ticket || s.state == 0) { isx_set_error("isx_pipe_collect: unknown or already released ticket"); return ISX_ERR_STATE; }
-        p->cv_done.wait(lk, [&] { return s.state == 2; });
+        if (s.tk.ticket != ticket || s.tk.state == 0) { isx_set_error("isx_pipe_collect: unknown or already released ticket"); return ISX_ERR_STATE; }
+        p->cv_done.wait(lk, [&] { return s.tk.state == 2; });
         out->collect_wait_ms = (float)(now_ms() - t0);
-        if (s.rc != ISX_OK) { isx_set_error(s.err); return s.rc; }
+        if (s.tk.rc != ISX_OK) { isx_set_error(s.tk.err); return s.tk.rc; }
     }
     HIP_TRY(hipSetDevice(c->device));
     out->ticket = ticket;
     out->n_pos = b->n_pos; out->n_obs = b->n_obs;
     out->sizes = b->sizes;
-    out->snv = (size_t)b->sizes.n_snv > p->snv_prefix ? s.snv_big.data() : reinterpret_cast<const isx_snv *>(s.h_small + s.o_snv);
+    out->snv = (size_t)b->sizes.n_snv > p->snv_prefix ? s.res.snv_big.data() : reinterpret_cast<const isx_snv *>(s.res.h_small + s.res.o_snv);
     if (dense) {
-        if (s.cov4) {
-            out->coverage4 = s.h_out + s.o_cov16;
-            out->cov_rows = reinterpret_cast<const uint16_t *>(s.h_out + s.o_cov16 + s.cov_rows_off);
-            out->cov_row_window = s.cov_row_win.data();
-            out->n_cov_rows = (int64_t)s.cov_row_win.size();
-            out->cov_window = s.cov_window;
-        } else if (s.cov8) out->coverage8 = s.h_out + s.o_cov16;
-        else out->coverage16 = reinterpret_cast<const uint16_t *>(s.h_out + s.o_cov16);
-        if (s.clon_sparse) { out->clon_sparse = reinterpret_cast<const isx_rare *>(s.h_out + s.o_clon); out->n_clon = (int64_t)b->n_clon; }
-        else out->clon = reinterpret_cast<const float *>(s.h_out + s.o_clon);
+        if (s.res.landed.cov4) {
+            out->coverage4 = s.res.h_out + s.res.o_cov16;
+            out->cov_rows = reinterpret_cast<const uint16_t *>(s.res.h_out + s.res.o_cov16 + s.res.landed.cov_rows_off);
+            out->cov_row_window = s.res.cov_row_win.data();
+            out->n_cov_rows = (int64_t)s.res.cov_row_win.size();
+            out->cov_window = s.res.landed.cov_window;
+        } else if (s.res.landed.cov8) out->coverage8 = s.res.h_out + s.res.o_cov16;
+        else out->coverage16 = reinterpret_cast<const uint16_t *>(s.res.h_out + s.res.o_cov16);
+        if (s.res.landed.clon_sparse) { out->clon_sparse = reinterpret_cast<const isx_rare *>(s.res.h_out + s.res.o_clon); out->n_clon = (int64_t)b->n_clon; }
+        else out->clon = reinterpret_cast<const float *>(s.res.h_out + s.res.o_clon);
         out->n_saturated = b->n_sat;
-        out->saturated = s.sat_complete ? s.sat_rows.data() : nullptr;
+        out->saturated = s.res.landed.sat_complete ? s.res.sat_rows.data() : nullptr;
         if (p->prm.rarefied_coverage > 0) {
             out->n_rare = (int64_t)b->n_rare;
-            if (!s.rare_dense) out->rare = s.rare_big.empty() ? reinterpret_cast<const isx_rare *>(s.h_small + s.o_rare) : s.rare_big.data();
-            if (p->pp.want_counts) out->clon_rarefied = reinterpret_cast<const float *>(s.h_out + s.o_clonr);
-            else if (s.rare_dense) out->clon_rarefied = s.clonr_big.data();
+            if (!s.res.landed.rare_dense) out->rare = s.res.rare_big.empty() ? reinterpret_cast<const isx_rare *>(s.res.h_small + s.res.o_rare) : s.res.rare_big.data();
+            if (p->pp.want_counts) out->clon_rarefied = reinterpret_cast<const float *>(s.res.h_out + s.res.o_clonr);
+            else if (s.res.landed.rare_dense) out->clon_rarefied = s.res.clonr_big.data();
         }
-        if (p->pp.want_counts) out->counts = reinterpret_cast<const uint32_t *>(s.h_out + s.o_counts);
+        if (p->pp.want_counts) out->counts = reinterpret_cast<const uint32_t *>(s.res.h_out + s.res.o_counts);
     }
     if (b->lev_sparse) {
-        out->lev_mask = s.h_out + s.o_lmask;
-        out->lev_win_off = reinterpret_cast<const uint32_t *>(s.h_out + s.o_lwin);
-        out->lev_cov = s.lcov_big.empty() ? s.h_out + s.o_lcov : s.lcov_big.data();
-        out->lev_clon = s.lclon_big.empty() ? reinterpret_cast<const isx_rare *>(s.h_out + s.o_lclon) : s.lclon_big.data();
-        out->lev_rare = s.lrare_big.empty() ? reinterpret_cast<const isx_rare *>(s.h_out + s.o_lrare) : s.lrare_big.data();
-        out->lev_sat = s.sat_rows.data();
+        out->lev_mask = s.res.h_out + s.res.o_lmask;
+        out->lev_win_off = reinterpret_cast<const uint32_t *>(s.res.h_out + s.res.o_lwin);
+        out->lev_cov = s.res.lcov_big.empty() ? s.res.h_out + s.res.o_lcov : s.res.lcov_big.data();
+        out->lev_clon = s.res.lclon_big.empty() ? reinterpret_cast<const isx_rare *>(s.res.h_out + s.res.o_lclon) : s.res.lclon_big.data();
+        out->lev_rare = s.res.lrare_big.empty() ? reinterpret_cast<const isx_rare *>(s.res.h_out + s.res.o_lrare) : s.res.lrare_big.data();
+        out->lev_sat = s.res.sat_rows.data();
         out->n_lev = b->sizes.n_entries; out->n_lev_clon = (int64_t)b->n_clon; out->n_lev_sat = (int64_t)b->n_sat;
         out->n_lev_rare = p->prm.rarefied_coverage > 0 ? (int64_t)b->n_rare : 0;
-        out->lev_mask_bytes = b->lev_mask_bytes; out->lev_cov_bytes = b->lev_cov_bytes;
+        out->lev_mask_bytes = b->lev_mask_bytes; out->lev_cov_bytes = s.res.landed.lev_cov_bytes;
         out->lev_window = b->W; out->n_lev_windows = b->n_win; out->lev_min_cov = p->prm.min_cov;
     }
     out->batch = b;
-    out->encode_ms = s.encode_ms;
-    out->encode_passes = s.encode_passes;
+    out->encode_ms = s.in.encode_ms;
+    out->encode_passes = s.in.encode_passes;
     out->record_bytes = p->rb;
-    out->h2d_bytes = s.h2d_bytes; out->d2h_bytes = s.d2h_bytes;
-    out->ld = p->prm.enable_linkage ? s.ld_rows.data() : nullptr;
-    out->rows_checksum = s.rows_checksum;
+    out->h2d_bytes = s.in.h2d_bytes; out->d2h_bytes = s.res.d2h_bytes;
+    out->ld = p->prm.enable_linkage ? s.res.ld_rows.data() : nullptr;
+    out->rows_checksum = s.res.rows_checksum;
     float ms = 0.f;
-    if (s.h2d_split) {                          // the time the DMA engine worked for this batch, not the stager's time between its two parts
+    if (s.in.h2d_split) {                          // the time the DMA engine worked for this batch, not the stager's time between its two parts
         float m1 = 0.f, m2 = 0.f;
-        if (hipEventElapsedTime(&m1, s.ev_h2d0, s.ev_h2da) == hipSuccess && hipEventElapsedTime(&m2, s.ev_h2db, s.ev_h2d1) == hipSuccess) out->h2d_ms = m1 + m2;
-    } else if (hipEventElapsedTime(&ms, s.ev_h2d0, s.ev_h2d1) == hipSuccess) out->h2d_ms = ms;
-    if (hipEventElapsedTime(&ms, s.ev_d2h0, s.ev_d2h1) == hipSuccess) out->d2h_ms = ms;
+        if (hipEventElapsedTime(&m1, s.in.ev_h2d0, s.in.ev_h2da) == hipSuccess && hipEventElapsedTime(&m2, s.in.ev_h2db, s.in.ev_h2d1) == hipSuccess) out->h2d_ms = m1 + m2;
+    } else if (hipEventElapsedTime(&ms, s.in.ev_h2d0, s.in.ev_h2d1) == hipSuccess) out->h2d_ms = ms;
+    if (hipEventElapsedTime(&ms, s.res.ev_d2h0, s.res.ev_d2h1) == hipSuccess) out->d2h_ms = ms;
     isx_timings t{};
     if (isx_batch_timings(b, &t) == ISX_OK) out->kernel_ms = t.pileup_ms;
     return ISX_OK;
@@ -1945,7 +2128,7 @@ static int pipe_fetch_entries(isx_pipe *p, int64_t ticket, isx_entry *out, const
     Slot &s = p->slots[(size_t)(ticket % (int64_t)p->slots.size())];
     {
         std::lock_guard<std::mutex> lk(p->mu);
-        if (s.ticket != ticket || s.state != 2 || s.rc != ISX_OK) { isx_set_error("isx_pipe_fetch_entries: collect the batch first"); return ISX_ERR_STATE; }
+        if (s.tk.ticket != ticket || s.tk.state != 2 || s.tk.rc != ISX_OK) { isx_set_error("isx_pipe_fetch_entries: collect the batch first"); return ISX_ERR_STATE; }
     }
     isx_batch *b = s.b;
     if (b->M == 1) { isx_set_error("n_mm_bins == 1: the dense tables come with isx_pipe_collect"); return ISX_ERR_STATE; }
@@ -1966,7 +2149,7 @@ static int pipe_fetch_entries(isx_pipe *p, int64_t ticket, isx_entry *out, const
     const size_t piece = std::min<size_t>((size_t)32 << 20, region / 2 / 4096 * 4096);
     if (piece < ((size_t)1 << 20))              // tiny pipe: the staging detour is not worth it
         return fetch_entries_sorted(p->ctx->stream, b->d_entries, b->d_win_nent, (uint32_t)b->slab, entry_wins(b), b->n_ovf, n, out, nullptr, soa);
-    uint8_t *bounce[2] = {s.h_in + s.off_rec, s.h_in + s.off_rec + piece};
+    uint8_t *bounce[2] = {s.in.h_in + s.in.off_rec, s.in.h_in + s.in.off_rec + piece};
     hipEvent_t ev[2] = {nullptr, nullptr};
     for (hipEvent_t &e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const EntryCopier copier = [&](const void *dsrc, void *hdst, size_t bytes, hipStream_t st) -> int {
@@ -2002,9 +2185,9 @@ int isx_pipe_release(isx_pipe *p, int64_t ticket)
     Slot &s = p->slots[(size_t)(ticket % (int64_t)p->slots.size())];
     std::unique_lock<std::mutex> lk(p->mu);
     if (ticket < p->next_promise) p->cv_done.wait(lk, [&] { return p->next_ticket > ticket; });
-    if (s.ticket != ticket || s.state == 0) { isx_set_error("isx_pipe_release: unknown or already released ticket"); return ISX_ERR_STATE; }
-    p->cv_done.wait(lk, [&] { return s.state == 2; });     // never collected: its queued work drains before the slot is reused
-    s.state = 0;
+    if (s.tk.ticket != ticket || s.tk.state == 0) { isx_set_error("isx_pipe_release: unknown or already released ticket"); return ISX_ERR_STATE; }
+    p->cv_done.wait(lk, [&] { return s.tk.state == 2; });     // never collected: its queued work drains before the slot is reused
+    s.tk.state = 0;
     return ISX_OK;
 }
 

@@ -249,29 +249,48 @@ def test_jumping_stream_learns_its_slack(ctx):
     pipe.close()
 
 
-def test_tables_grow_inside_a_slot(ctx):
+@pytest.mark.parametrize("want_counts,rarefied", [(False, 0), (True, 5)])
+def test_tables_grow_inside_a_slot(ctx, want_counts, rarefied):
     """SNS rows at every position outgrow the slot's SNV table: collect grows it, repeats the pass and still
-    returns the right tables; the next batch in the same slot is unaffected"""
+    returns the right tables; the next batch in the same slot is unaffected.  (True, 5): the repeated pass of a slot
+    with a pinned result block, a count table and a dense clonTR table (every position reaches coverage 5) -- the
+    tables that left with the first pass are fetched again; counts and clon_r byte for byte the one-shot batch's"""
     from instrain_amd import engine
     n_pos, depth = 1_200_000, 6
     pos = np.repeat(np.arange(n_pos, dtype=np.uint32), depth)
     obs = engine.pack_obs(pos, np.ones(len(pos), np.uint8), np.zeros(len(pos), int))
     ref = np.zeros(n_pos, np.uint8)
+    kw = dict(enable_linkage=False)
+    if rarefied:                # (0: the default of 50 on both sides, which depth 6 never reaches -- the case as it always ran)
+        kw["rarefied_coverage"] = rarefied
+
+    def same_full(r, exp, what):
+        for k in ("counts", "clon_r"):
+            assert r[k].dtype.itemsize == exp[k].dtype.itemsize and r[k].shape == exp[k].shape, (what, k)
+            assert r[k].tobytes() == exp[k].tobytes(), (what, k)
+
     pipe = engine.Pipe(ctx, max_pos=n_pos, max_obs=len(obs), max_splits=16, depth=2, host_threads=4, n_mm_bins=1,
-                       enable_linkage=False)
+                       want_counts=want_counts, **kw)
     t = pipe.submit(ref, [0, n_pos], obs)
     r = pipe.collect(t)
     assert r["sizes"]["n_snv"] == n_pos and (r["snv"]["cls"] == 2).all() and (r["snv"]["gpos"] == np.arange(n_pos)).all()
     assert (r["snv"]["cnt"][:, 1] == depth).all() and (r["snv"]["cnt"][:, [0, 2, 3]] == 0).all()
-    assert (r["cov16"] == depth).all() and (r["clon"] == 1.0).all() and len(r["rare"]) == 0
+    assert (r["cov16"] == depth).all() and (r["clon"] == 1.0).all() and len(r["rare"]) == (n_pos if rarefied else 0)
+    if want_counts:
+        big = {"ref_codes": ref, "split_bounds": np.array([0, n_pos], np.int64), "obs": obs, "pair": None, "n_mm_bins": 1}
+        exp_big, sizes_big = one_shot(ctx, big, **kw)
+        assert r["sizes"] == sizes_big
+        same_full(r, exp_big, "repeated pass")
     pipe.release(t)
     w = small_workload(500, 40_000, 20, True)
-    exp, sizes = one_shot(ctx, w, enable_linkage=False)
+    exp, sizes = one_shot(ctx, w, **kw)
     t2 = pipe.submit(w["ref_codes"], w["split_bounds"], w["obs"])
     t3 = pipe.submit(w["ref_codes"], w["split_bounds"], w["obs"])
     for t in (t2, t3):
         r = pipe.collect(t)
         same_tables(r, exp, "after growth")
+        if want_counts:
+            same_full(r, exp, "after growth")
         pipe.release(t)
     pipe.close()
 
